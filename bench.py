@@ -25,7 +25,14 @@ torch.distributed.run when started without WORLD_SIZE, one process per GPU):
 The C5 destriper leg is weak-scaled (8 observations per GPU) with an RCCL
 all-reduce of the map numerator and CG scalars every iteration.
 
-    python bench.py [--gpus N --steps K --warmup W --mode shard|obs]
+A plain run sets up the observation, warms up, times ``--steps`` steps and prints the
+result line (with the streaming passes' roofline, whose HIP events are recorded inside
+the timed steps).  ``--full`` adds every secondary leg after the timed steps: per-kernel
+times, the C4 / C5 / field destriper legs, the L1 -> maps chain, the host-cube leg and
+the CPU baselines.  ``--dump-outputs DIR`` writes the last timed step's Level-2 datasets
+to DIR as .npy (dump_outputs).
+
+    python bench.py [--gpus N --steps K --warmup W --mode shard|obs --full --dump-outputs DIR]
 """
 import argparse
 import json
@@ -70,7 +77,70 @@ def parse():
     ap.add_argument('--no-chain', action='store_true', help='skip the L1 -> L2 -> maps chain leg')
     ap.add_argument('--shard-of', type=int, default=0,
                     help='measurement aid: reduce only rank 0\'s C3 shard of an N-way split, in this one process')
-    return ap.parse_args()
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also run every secondary leg: per-kernel times, the C4 / C5 / field '
+                         'destriper legs, the L1 -> maps chain, the host-cube leg and the CPU baselines '
+                         '(each still subject to its own --no-* / --c5-* option)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the Level-2 datasets of the last timed step (rank 0) to DIR/<name>.npy')
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
+
+
+# ---------------------------------------------------------------- outputs of the timed path
+DUMP_WHOLE_BYTES = 4 << 20          # datasets up to this size are written whole
+DUMP_SAMPLE = 1_000_000             # elements kept of a larger one (8 MB as f64)
+DUMP_SEED = 20240601
+# not computed by this path: Level1AveragingGainCorrection hands these back as zero-filled
+# host arrays of the reference's shapes (the power-spectrum fit is a stage of its own)
+DUMP_SKIP = ('averaged_tod/frequency_power_spectra', 'averaged_tod/frequency_power_spectra_fits')
+
+
+def dump_outputs(level2, outdir):
+    """Write every computed dataset of a reduced observation's Level-2 (what reduce_step's
+    caller receives, less the DUMP_SKIP placeholders) as ``outdir/<path with / as __>.npy``: f32 / f64 as computed, anything else
+    as f64.  A dataset above DUMP_WHOLE_BYTES is written as a fixed sample: DUMP_SAMPLE
+    elements of the flattened array at sorted indices drawn without replacement by
+    numpy's default_rng(DUMP_SEED), the same indices for every dataset of that size and
+    in every run: at most 8 MB per dataset, 7 datasets.
+
+    Every file holds finite numbers only.  The reduction marks what it did not compute
+    with NaN, as the reference does (atmosphere/fit_values of a channel without a fit);
+    a dataset with such elements is written with 0 in their place, and their positions
+    go to ``<name>__nonfinite.npy`` (f32, same shape: 0 finite, 1 NaN, 2 +inf, 3 -inf),
+    so the pattern is compared like any other output (at most 4 MB more per dataset)."""
+    import torch
+    os.makedirs(outdir, exist_ok=True)
+    picks = {}
+    for key, v in level2.items():
+        if v is None or key in DUMP_SKIP:
+            continue
+        if not isinstance(v, torch.Tensor):
+            v = np.asarray(v)
+        n = int(v.numel()) if isinstance(v, torch.Tensor) else int(v.size)
+        flat = v.reshape(-1)
+        if n * 8 > DUMP_WHOLE_BYTES:
+            if n not in picks:
+                picks[n] = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False))
+            idx = picks[n]
+            flat = flat[torch.from_numpy(idx).to(v.device)] if isinstance(v, torch.Tensor) else flat[idx]
+        a = flat.detach().cpu().numpy() if isinstance(flat, torch.Tensor) else np.asarray(flat)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        if n * 8 <= DUMP_WHOLE_BYTES:
+            a = a.reshape(tuple(v.shape))
+        name = key.replace('/', '__')
+        fin = np.isfinite(a)
+        if not fin.all():
+            code = np.zeros(a.shape, np.float32)
+            code[np.isnan(a)] = 1
+            code[np.isposinf(a)] = 2
+            code[np.isneginf(a)] = 3
+            np.save(os.path.join(outdir, name + '__nonfinite.npy'), code)
+            a = np.where(fin, a, a.dtype.type(0))
+        np.save(os.path.join(outdir, name + '.npy'), a)
 
 
 # ---------------------------------------------------------------- N-GPU launch
@@ -773,8 +843,9 @@ def main():
     for _ in range(max(args.warmup, 1)):       # the first step also creates the plan
         level2 = reduce_step(data, device)
     obs = data._gpu_observation
-    # timed region: HIP events around the three streaming passes only (the roofline's
-    # kernel); the per-kernel breakdown comes from extra untimed steps below
+    # timed region: host wall time around args.steps full reductions; HIP events around the
+    # three streaming passes only (the roofline's kernel) are recorded inside it, and the
+    # per-kernel breakdown comes from extra untimed steps below (--full)
     obs.profile(1)
     obs.profile_collect()
     torch.cuda.synchronize()
@@ -791,11 +862,15 @@ def main():
         dist.barrier()
     elapsed = t1 - t0
     prof = obs.profile_collect()
-    obs.profile(2)
-    n_kprof = max(1, min(args.steps, 3))
-    for _ in range(n_kprof):
-        level2 = reduce_step(data, device)
-    kprof = obs.profile_collect()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(level2, args.dump_outputs)      # the last timed step's Level-2
+    kprof, n_kprof = None, 0
+    if args.full:
+        obs.profile(2)
+        n_kprof = max(1, min(args.steps, 3))
+        for _ in range(n_kprof):
+            level2 = reduce_step(data, device)
+        kprof = obs.profile_collect()
     obs.profile(False)
     rank_ms = None
     if world > 1:
@@ -808,37 +883,40 @@ def main():
     frac = obs.pass_fractions()
     vane_search_ms = getattr(obs, 'last_vane_search_ms', None)
     check = check_against_oracle(data, level2, device) if (args.check and rank == 0) else None
+    # the secondary legs run only with --full
+    want_destriper = args.full and not args.no_destriper
+    want_cpu = args.full and not args.no_cpu_baseline and world == 1
     dstr = None
-    if not args.no_destriper and not shard:
+    if want_destriper and not shard:
         dstr = destriper_leg(level2, data, args.destriper_iters, device,
-                             want_cpu=(rank == 0 and world == 1 and not args.no_cpu_baseline))
+                             want_cpu=(rank == 0 and want_cpu))
         if world > 1:
             v = torch.tensor([dstr['cg_iters_per_s']], device='cuda', dtype=torch.float64)
             dist.all_reduce(v, op=dist.ReduceOp.MIN)
             dstr['cg_iters_per_s_min_over_ranks'] = float(v.item())
 
     chain = None
-    if not args.no_destriper and not shard and world == 1 and not args.no_chain:
+    if want_destriper and not shard and world == 1 and not args.no_chain:
         scan_sc0 = sh.samples_x_channels()
         l1_bytes = sum(ALGO_BYTES_PER_SAMPCH_PASS * scan_sc0 * frac[k] for k in type_streaming())
         chain = chain_leg(data, device, l1_bytes)
 
     c5 = None
-    if not args.no_destriper and args.c5_obs > 0:
+    if want_destriper and args.c5_obs > 0:
         del data, level2, obs
         torch.cuda.empty_cache()
         c5 = destriper_c5_leg(args.c5_obs, args.destriper_iters, device, world, rank)
         torch.cuda.empty_cache()
         c5['bands4'] = destriper_c5_leg(args.c5_obs, args.destriper_iters, device, world, rank, n_bands=4)
     c5f = None
-    if not args.no_destriper and args.c5_field_obs > 0:
+    if want_destriper and args.c5_field_obs > 0:
         if c5 is None:
             del data, level2, obs
         torch.cuda.empty_cache()
         c5f = destriper_c5_field_leg(args.c5_field_obs, args.destriper_iters, device, world, rank)
 
     e2e = None
-    if not args.no_e2e and world == 1:
+    if args.full and not args.no_e2e and world == 1:
         e2e = e2e_leg(F, T, device)
 
     if rank == 0:
@@ -899,14 +977,15 @@ def main():
                                  # same reduction in 3 (a work saving, not a bandwidth figure)
                                  'survey_4pass_bytes': SURVEY_BYTES_PER_SAMPCH * scan_sc,
                                  'work_saving_vs_survey_4pass': SURVEY_BYTES_PER_SAMPCH * scan_sc / design_bytes},
-            'kernel_ms_per_step': {k: v[0] / n_kprof for k, v in kprof.items()},
-            'kernel_ms_note': f'HIP events around every kernel, {n_kprof} extra steps after the timed region',
             'host_stage_ms_per_step': {k: v / args.steps for k, v in host_ms.items()},
             'host_vane_search_ms': vane_search_ms,
             'pass_GBs': {k: pass_bytes[k] / (stream[k][0] / args.steps * 1e-3) / 1e9
                          for k in type_streaming() if stream[k][1] > 0},
             'launches_per_step': {k: stream[k][1] / args.steps for k in type_streaming()},
         }
+        if kprof is not None:
+            line['kernel_ms_per_step'] = {k: v[0] / n_kprof for k, v in kprof.items()}
+            line['kernel_ms_note'] = f'HIP events around every kernel, {n_kprof} extra steps after the timed region'
         if dstr is not None:
             line['destriper'] = dstr
         if c5 is not None:
@@ -921,7 +1000,7 @@ def main():
             line['end_to_end_host'] = e2e
         if check is not None:
             line['check'] = check
-        if not args.no_cpu_baseline and world == 1:
+        if want_cpu:
             cb = cpu_baseline()
             if dstr is not None and 'cpu_port' in dstr:
                 cb['destriper_port'] = dstr.pop('cpu_port')

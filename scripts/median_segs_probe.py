@@ -16,7 +16,7 @@ def main():
     for t in specs:
         extra = dict(kv.split('=') for kv in t.split(',')) if '=' in t else {'COMAP_MEDIAN_WMSEGS': t}
         env = dict(os.environ, **extra)
-        out = subprocess.run([sys.executable, 'bench.py', '--steps', '3', '--warmup', '1', '--no-e2e',
+        out = subprocess.run([sys.executable, 'bench.py', '--steps', '3', '--warmup', '1', '--full', '--no-e2e',
                               '--no-cpu-baseline', '--c5-obs', '0', '--c5-field-obs', '0'],
                              env=env, capture_output=True, text=True, timeout=280)
         line = next((l for l in out.stdout.splitlines() if l.startswith('{')), None)

@@ -38,34 +38,47 @@ def test_medfilt_reference_build_matches_golden(golden_dir):
         assert np.array_equal(oracle.medfilt_reference(x.copy(), w), g[f'medfilt_{seed}_{n}_{w}'])
 
 
-def test_medfilt_oracle_vs_reference_random():
-    if oracle.ref_lib() is None:
-        pytest.skip('oracle/_ref not built')
-    rng = np.random.default_rng(5)
-    for n, w in [(3000, 6), (2500, 401), (1000, 3), (7000, 2000)]:
-        x = np.round(rng.standard_normal(n), 1)     # many ties
-        assert np.array_equal(oracle.medfilt(x.copy(), w), oracle.medfilt_reference(x.copy(), w))
+def _ref_cases(golden_dir):
+    import sys
+    sys.path.insert(0, golden_dir)
+    import medfilt_ref_cases
+    return medfilt_ref_cases, np.load(os.path.join(golden_dir, 'golden_medfilt_ref.npz'))
 
 
-def test_medfilt_oracle_vs_reference_infinities():
+def _reference_answer(g, key, x, w):
+    """The reference's compiled filter() on (x, w): its stored answer
+    (tests/golden/make_medfilt_ref.py), which the live build (oracle/_ref), where there
+    is one, must reproduce."""
+    want = g[key]
+    assert want.shape == x.shape, key
+    if oracle.ref_lib() is not None:
+        assert np.array_equal(oracle.medfilt_reference(x.copy(), w), want, equal_nan=True), key
+    return want
+
+
+def test_medfilt_oracle_vs_reference_random(golden_dir):
+    mc, g = _ref_cases(golden_dir)
+    cases = list(mc.ties())                          # many ties
+    assert len(cases) == 4
+    for key, x, w in cases:
+        want = _reference_answer(g, key, x, w)
+        assert np.isfinite(want).all(), key
+        assert np.array_equal(oracle.medfilt(x.copy(), w), want), key
+
+
+def test_medfilt_oracle_vs_reference_infinities(golden_dir):
     """+-inf samples (scattered, a run making window medians +inf, a run whose windows'
     middle pair is -inf / +inf): the order-statistics oracle == the reference's compiled
     two-heap filter, NaN results included."""
-    if oracle.ref_lib() is None:
-        pytest.skip('oracle/_ref not built')
-    rng = np.random.default_rng(31)
-    for n, w in [(5000, 400), (4000, 401), (3000, 6), (9000, 6000), (2000, 1)]:
-        x = np.round(rng.standard_normal(n), 1)
-        x[rng.random(n) < 0.03] = np.inf
-        x[rng.random(n) < 0.03] = -np.inf
-        a = n // 3
-        x[a:a + 300] = np.inf
-        x[a + 300:a + 600] = -np.inf
-        want = oracle.medfilt_reference(x.copy(), w)
+    mc, g = _ref_cases(golden_dir)
+    cases = list(mc.infinities())
+    assert len(cases) == 5
+    for key, x, w in cases:
+        want = _reference_answer(g, key, x, w)
         got = oracle.medfilt(x.copy(), w)
-        assert np.array_equal(got, want, equal_nan=True), (n, w)
+        assert np.array_equal(got, want, equal_nan=True), key
         if w <= 401:                               # the 300-runs dominate these windows
-            assert np.isinf(want).any() and (w % 2 or np.isnan(want).any()), (n, w)
+            assert np.isinf(want).any() and (w % 2 or np.isnan(want).any()), key
 
 
 def _nan_cases(golden_dir):
@@ -91,22 +104,16 @@ def test_medfilt_twoheap_vs_nan_fixtures(golden_dir):
         assert np.array_equal(got, y, equal_nan=True), name
 
 
-def test_medfilt_twoheap_vs_reference_random():
-    """Random NaN / +-inf / n < w series: the two-heap restatement == oracle/_ref."""
-    if oracle.ref_lib() is None:
-        pytest.skip('oracle/_ref not built')
-    rng = np.random.default_rng(77)
-    for _ in range(150):
-        n = int(rng.integers(1, 2500))
-        w = int(rng.integers(1, 700))
-        if n < w // 2 + w % 2:
-            continue
-        x = np.round(rng.standard_normal(n), 1)
-        x[rng.random(n) < rng.choice([0.0, 0.01, 0.2])] = np.nan
-        x[rng.random(n) < 0.01] = rng.choice([np.inf, -np.inf])
-        want = oracle.medfilt_reference(x.copy(), w)
-        assert np.array_equal(oracle.medfilt_twoheap(x.copy(), w), want, equal_nan=True), (n, w)
-        assert np.array_equal(oracle.medfilt(x.copy(), w), want, equal_nan=True), (n, w)
+def test_medfilt_twoheap_vs_reference_random(golden_dir):
+    """Random NaN / +-inf / n < w series: the two-heap restatement == the reference's
+    compiled filter (stored answers; oracle/_ref too where it is built)."""
+    mc, g = _ref_cases(golden_dir)
+    cases = list(mc.twoheap_random())
+    assert len(cases) == 142                         # of 150 draws, those with n >= ceil(w / 2)
+    for key, x, w in cases:
+        want = _reference_answer(g, key, x, w)
+        assert np.array_equal(oracle.medfilt_twoheap(x.copy(), w), want, equal_nan=True), key
+        assert np.array_equal(oracle.medfilt(x.copy(), w), want, equal_nan=True), key
 
 
 def test_binvalues_oracle_bit_exact(golden_dir):
