@@ -5,7 +5,7 @@
 on rank 0 and ``None`` maps on other ranks.  Internally:
 
 * ``DeviceOps`` -- one rank's samples as the constant offset<->pixel sparse
-  operator built by ``comap_destripe_create`` (destriper_kernels.hip);
+  operator built by ``comap_destripe_create`` (csrc/destriper_setup.hip);
 * ``cg_solve`` -- the reference BiCG (Destriper.py:85-152) with its two
   duplicate matvecs folded (p == pb, r == rb), run on device vectors; per
   iteration the only exchange is a SUM all-reduce of the map numerator
@@ -151,7 +151,23 @@ def cg_solve_batched(ops, allreduce, threshold=1e-6, niter=100, batch=16):
     problem at once (vectors interleaved [n][nb], one all-reduce per sum for
     all bands).  Returns (x in the problem's internal offset order -- see
     DeviceOps.natural --, iterations per band (list), h, nnum)."""
-    torch = ops.torch
+    nb = ops.nb
+    x, h, nnum, flags, iteration = _dist_start(ops, allreduce, threshold)
+    enq = 0
+    while enq < niter:
+        k = min(batch, niter - enq)
+        for _ in range(k):
+            iteration()
+        enq += k
+        if int(flags[0].item()):
+            break
+    return x, [int(v) for v in flags[2 + nb:2 + 2 * nb].tolist()], h, nnum
+
+
+def _dist_start(ops, allreduce, threshold):
+    """The batched multi-rank CG drivers' common start: the global weight map and naive
+    numerator, x = 0, r = p = b, the device scalars and stop flags, and the iteration
+    closure over them.  Returns (x, h, nnum, flags, iteration)."""
     nb = ops.nb
     h0, _, n0 = ops.local_maps()
     h = allreduce(h0)
@@ -167,17 +183,8 @@ def cg_solve_batched(ops, allreduce, threshold=1e-6, niter=100, batch=16):
     scal[nb:2 * nb].copy_(scal[0:nb])
     scal[3 * nb:4 * nb].copy_(scal[0:nb])
     scal[4 * nb] = float(threshold)
-    flags = torch.zeros(2 + 2 * nb, dtype=torch.int32, device=ops.dev)
-    iteration = _dist_iteration(ops, allreduce, p, num, h, q, scal, flags, x, r)
-    enq = 0
-    while enq < niter:
-        k = min(batch, niter - enq)
-        for _ in range(k):
-            iteration()
-        enq += k
-        if int(flags[0].item()):
-            break
-    return x, [int(v) for v in flags[2 + nb:2 + 2 * nb].tolist()], h, nnum
+    flags = ops.torch.zeros(2 + 2 * nb, dtype=ops.torch.int32, device=ops.dev)
+    return x, h, nnum, flags, _dist_iteration(ops, allreduce, p, num, h, q, scal, flags, x, r)
 
 
 def _dist_iteration(ops, allreduce, p, num, h, q, scal, flags, x, r):
@@ -220,22 +227,7 @@ def cg_solve_graph(ops, allreduce, threshold=1e-6, niter=100, batch=16):
     remainder niter % batch runs eagerly.  Returns like cg_solve_batched."""
     torch = ops.torch
     nb = ops.nb
-    h0, _, n0 = ops.local_maps()
-    h = allreduce(h0)
-    nnum = allreduce(n0)
-    NO = ops.n_offsets
-    x, r, q = ops.zeros(NO * nb), ops.zeros(NO * nb), ops.zeros(NO * nb)
-    num = ops.zeros(ops.npix * nb)
-    ops.project(None, nnum, h, r)
-    p = ops.copy(r)
-    scal = ops.zeros(4 * nb + 1)
-    ops.dot(r, r, scal[0:nb])
-    allreduce(scal[0:nb])
-    scal[nb:2 * nb].copy_(scal[0:nb])
-    scal[3 * nb:4 * nb].copy_(scal[0:nb])
-    scal[4 * nb] = float(threshold)
-    flags = torch.zeros(2 + 2 * nb, dtype=torch.int32, device=ops.dev)
-    iteration = _dist_iteration(ops, allreduce, p, num, h, q, scal, flags, x, r)
+    x, h, nnum, flags, iteration = _dist_start(ops, allreduce, threshold)
 
     nfull = niter // batch
     graph = None
