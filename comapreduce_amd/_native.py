@@ -97,6 +97,20 @@ _SIGS = {
     'comap_relabel_pixels_tiled': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int32, c_void_p]),
     'comap_destripe_solve': (c_int, [c_void_p, c_double, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p, P_int32]),
+    'comap_destripe_ground_create': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                             ctypes.POINTER(c_void_p)]),
+    'comap_destripe_ground_destroy': (c_int, [c_void_p]),
+    'comap_destripe_ground_n_groups': (c_int64, [c_void_p]),
+    'comap_destripe_ground_nnz': (c_int, [c_void_p, P_int64, P_int64]),
+    'comap_destripe_ground_stats': (c_int, [c_void_p, c_void_p, c_void_p]),
+    'comap_destripe_ground_fold': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    'comap_destripe_ground_bin': (c_int, [c_void_p, c_void_p, c_void_p]),
+    'comap_destripe_ground_project': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'comap_destripe_ground_rhs': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'comap_destripe_ground_tail_dot': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    'comap_destripe_ground_tail_update': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                  c_void_p]),
+    'comap_destripe_ground_tail_direction': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'comap_prep_auto_rms': (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int64, c_void_p]),
     'comap_prep_percentiles': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_int64,
                                        c_void_p]),

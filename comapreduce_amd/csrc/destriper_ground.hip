@@ -1,0 +1,754 @@
+// destriper_ground.hip -- the ground (azimuth) template of the destriper's CG: the reference's
+// op_Ax_with_ground (MapMaking/Destriper.py:265-336) on a problem built by destriper_setup.hip.
+//
+// Unknowns [x_0 .. x_{NO-1} | s_0 .. s_{K-1} | c_0 .. c_{K-1}]: one offset per L samples and, per
+// group k = (observation, feed), an azimuth slope s_k and a level c_k.  The template of sample t
+// (offset o, group k) is x_o + s_k a_t + c_k and the operator is A = [F G]^T W Z [F G] with the
+// plain destriper's binning, map division (m_p = num_p where h_p == 0) and m[pointing] wrap.
+//
+// Two deviations from the reference:
+//   1. a_t = (az_t - mu_k) / sigma_k with the plain mean and rms of the group's azimuths (a_t = 0
+//      when the group's azimuth is constant): the same model space -- the level absorbs the shift
+//      -- with a condition number CG can work with (raw degrees gave eigenvalues of 4.5e6).  The
+//      caller converts back: slope = s / sigma, level = c - s mu / sigma.
+//   2. every offset lies in ONE group (the caller passes a group id per offset).  The reference
+//      selects samples; the aggregated form below needs whole offsets.
+//
+// Aggregated form.  With g(o) the group of offset o, x'_o = x_o + c_{g(o)} (the level folded into
+// the offsets) and, per offset, wa_o = sum w a; per group, Saa_k = sum w a^2, Ta_k = sum w a tod;
+// per (group, pixel) entry e, ga_e = sum w a over the group's samples that fall in that pixel:
+//     num  = W x' (comap_destripe_bin)  +  sum_{e in pixel row p} ga_e s_{k(e)}     ground_bin
+//     y_o  = comap_destripe_project(x', num)  +  wa_o s_{g(o)}                      ground_project
+//     z1_k = sum_{o in k} y_o
+//     za_k = sum_{o in k} wa_o x'_o + Saa_k s_k - sum_{e in group row k} ga_e m[read pixel of e]
+//     rhs:  b1_k = sum_{o in k} b_o,  ba_k = Ta_k - sum_e ga_e m_naive[read pixel of e]
+// The plain destriper's kernels are used through their C ABI, unchanged.
+//
+// Layout: (group, pixel) entries twice, as the offset<->pixel operator is -- group-major for the
+// projection (off-map reads kept with their negative pixel id, as opix) and pixel-major for the
+// bin (binned entries only).  Both come from one stable radix sort of the samples by (group, read
+// pixel, off-map) with segment sums in sample order, so the build is deterministic.  Group rows
+// hold 1e4 .. 1e5 entries: they are cut into fixed chunks, one workgroup per chunk, and a finishing
+// kernel adds each group's partials in chunk order.  No floating-point atomics anywhere.
+#include "destriper_internal.h"
+
+#include <hipcub/hipcub.hpp>
+#include <rocprim/device/device_radix_sort.hpp>
+
+struct comap_ground {
+    comap_destriper *d = nullptr;
+    comap_ctx *ctx = nullptr;
+    int64_t NO = 0, npix = 0, K = 0;
+    int64_t nnz = 0;            // group-major entries (incl. off-map reads)
+    int64_t nnzb = 0;           // pixel-major entries (binned only)
+    // offsets (internal order, d->perm)
+    int32_t *gint = nullptr;    // [NO] group of internal offset i
+    int32_t *glist = nullptr;   // [NO] internal offsets sorted by group (stable)
+    double *wa = nullptr;       // [NO] sum w a
+    // groups
+    double *mu = nullptr, *sigma = nullptr, *saa = nullptr, *ta = nullptr;   // [K]
+    // group-major entries
+    int32_t *gpix = nullptr;    // [nnz] pixel (negative: an off-map read of m[npix + p])
+    double *ga = nullptr;       // [nnz]
+    // pixel-major entries
+    int64_t *gprow = nullptr;   // [npix + 1]
+    int32_t *gpk = nullptr;     // [nnzb] group
+    double *gpa = nullptr;      // [nnzb]
+    // reduction chunks: nce entry chunks then nco offset chunks, each (group, begin, end)
+    int64_t nce = 0, nco = 0;
+    int64_t *chunks = nullptr;  // [nce + nco][3]
+    int64_t *cgrp = nullptr;    // [2 (K + 1)] each group's entry-chunk range, then its offset-chunk range
+    double *part = nullptr;     // [nce + 2 nco] chunk partials
+};
+
+namespace {
+
+constexpr int64_t kChunkE = 1024;   // entries per projection workgroup (4 per thread: one pass of loads)
+constexpr int64_t kChunkO = 1024;   // offsets per workgroup
+constexpr int kBinLanes = 4;        // lanes per pixel row of the ground bin (rows hold <= K entries)
+
+__device__ __forceinline__ int64_t wrap_pixel(int32_t p, int64_t npix) { return p >= 0 ? (int64_t)p : npix + p; }
+
+__device__ __forceinline__ double map_value(const double *num, const double *h, int64_t q)
+{
+    const double hv = h[q];
+    return hv != 0.0 ? num[q] / hv : num[q];
+}
+
+__device__ __forceinline__ int64_t lb32(const int32_t *a, int64_t n, int64_t v)
+{
+    int64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const int64_t m = (lo + hi) >> 1;
+        if (a[m] < v) lo = m + 1; else hi = m;
+    }
+    return lo;
+}
+
+inline int bits_for(uint64_t bound)   // bits that hold every key in [0, bound)
+{
+    int b = 1;
+    while (b < 64 && (uint64_t(1) << b) < bound) ++b;
+    return b;
+}
+
+// fixed-order block sum (256 threads): wave sums, then the four waves' sums
+__device__ __forceinline__ double block_sum(double v, double *red)
+{
+    v = wave_sum(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// ---------------------------------------------------------------- set-up
+// gint[i] = gid[perm[i]] (flag[0]: an id outside [0, K)), val[i] = i
+__global__ void k_gr_gint(const int32_t *__restrict__ gid, const int32_t *__restrict__ perm, int64_t NO, int64_t K,
+                          int32_t *__restrict__ gint, int32_t *__restrict__ val, int32_t *__restrict__ flag)
+{
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < NO; i += (int64_t)gridDim.x * blockDim.x) {
+        int32_t g = gid[perm[i]];
+        if (g < 0 || g >= K) { flag[0] = 1; g = 0; }
+        gint[i] = g;
+        val[i] = (int32_t)i;
+    }
+}
+
+// row[k] = first sorted position with key >= k, k in [0, n_rows]
+__global__ void k_gr_rowptr(const int32_t *__restrict__ skey, int64_t n, int64_t n_rows, int64_t *__restrict__ row)
+{
+    for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k <= n_rows; k += (int64_t)gridDim.x * blockDim.x)
+        row[k] = lb32(skey, n, k);
+}
+
+// Per-offset sums over its L samples in sample order, a thread per internal offset i (offset
+// perm[i]).  PASS 0: sum az, min, max.  PASS 1: sum (az - mu)^2.  PASS 2: sum w a, sum w a^2,
+// sum w a tod with a = (az - mu) / sigma (0 when sigma == 0).
+template <int PASS>
+__global__ void __launch_bounds__(256) k_gr_offsets(const double *__restrict__ az, const double *__restrict__ w,
+                                                    const double *__restrict__ tod, const int32_t *__restrict__ perm,
+                                                    const int32_t *__restrict__ gint, const double *__restrict__ mu,
+                                                    const double *__restrict__ sigma, int64_t NO, int L,
+                                                    double *__restrict__ o0, double *__restrict__ o1,
+                                                    double *__restrict__ o2)
+{
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < NO; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t t0 = (int64_t)perm[i] * L;
+        const int32_t k = gint[i];
+        if constexpr (PASS == 0) {
+            double s = 0.0, mn = az[t0], mx = az[t0];
+            for (int j = 0; j < L; ++j) {
+                const double v = az[t0 + j];
+                s += v;
+                mn = fmin(mn, v);
+                mx = fmax(mx, v);
+            }
+            o0[i] = s; o1[i] = mn; o2[i] = mx;
+        } else if constexpr (PASS == 1) {
+            const double m = mu[k];
+            double s = 0.0;
+            for (int j = 0; j < L; ++j) {
+                const double v = az[t0 + j] - m;
+                s = fma(v, v, s);
+            }
+            o0[i] = s;
+        } else {
+            const double m = mu[k], sg = sigma[k];
+            double sa = 0.0, saa = 0.0, sat = 0.0;
+            for (int j = 0; j < L; ++j) {
+                const double a = sg > 0.0 ? (az[t0 + j] - m) / sg : 0.0;
+                const double wv = w[t0 + j] * a;
+                sa += wv;
+                saa = fma(wv, a, saa);
+                sat = fma(wv, tod[t0 + j], sat);
+            }
+            o0[i] = sa; o1[i] = saa; o2[i] = sat;
+        }
+    }
+}
+
+// out[k] = sum (OP 0), min (1) or max (2) of v over group k's offsets, one workgroup per group,
+// in a fixed order (thread-strided over the group's list, then the block)
+template <int OP>
+__global__ void __launch_bounds__(256) k_gr_group(const double *__restrict__ v, const int32_t *__restrict__ glist,
+                                                  const int64_t *__restrict__ grow, double *__restrict__ out)
+{
+    __shared__ double red[4];
+    const int64_t k = blockIdx.x, b = grow[k], e = grow[k + 1];
+    double acc = OP == 0 ? 0.0 : (OP == 1 ? INFINITY : -INFINITY);
+    for (int64_t j = b + threadIdx.x; j < e; j += 256) {
+        const double x = v[glist[j]];
+        acc = OP == 0 ? acc + x : (OP == 1 ? fmin(acc, x) : fmax(acc, x));
+    }
+    if constexpr (OP == 0) {
+        acc = block_sum(acc, red);
+    } else {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const double y = __shfl_xor(acc, o, 64);
+            acc = OP == 1 ? fmin(acc, y) : fmax(acc, y);
+        }
+        __syncthreads();
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+        __syncthreads();
+        acc = OP == 1 ? fmin(fmin(red[0], red[1]), fmin(red[2], red[3])) : fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+    }
+    if (threadIdx.x == 0) out[k] = acc;
+}
+
+// mu_k = sum az / n (0 for an empty group)
+__global__ void k_gr_mean(const double *__restrict__ sum, const int64_t *__restrict__ grow, int64_t K, int L,
+                          double *__restrict__ mu)
+{
+    for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < K; k += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t n = (grow[k + 1] - grow[k]) * L;
+        mu[k] = n ? sum[k] / (double)n : 0.0;
+    }
+}
+
+// sigma_k = sqrt(sum (az - mu)^2 / n); exactly 0 for an empty group or a constant azimuth
+// (min == max: the rounded mean of equal values need not equal them)
+__global__ void k_gr_rms(const double *__restrict__ sum, const double *__restrict__ mn, const double *__restrict__ mx,
+                         const int64_t *__restrict__ grow, int64_t K, int L, double *__restrict__ sigma)
+{
+    for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < K; k += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t n = (grow[k + 1] - grow[k]) * L;
+        sigma[k] = (n && mx[k] > mn[k]) ? sqrt(sum[k] / (double)n) : 0.0;
+    }
+}
+
+// Sort key of sample t: ((group, read pixel), off-map) -- the pixel the sample bins, or the
+// one its projection reads through the wrap.  flag[0]: a group id outside [0, K); flag[1]: a
+// pixel id outside [-npix, npix).
+__global__ void k_gr_keys(const int32_t *__restrict__ pix, const int32_t *__restrict__ gid, int64_t N, int L,
+                          int64_t npix, int64_t K, uint64_t *__restrict__ key, int32_t *__restrict__ val,
+                          int32_t *__restrict__ flag)
+{
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < N; t += (int64_t)gridDim.x * blockDim.x) {
+        int64_t k = gid[t / L];
+        if (k < 0 || k >= K) { flag[0] = 1; k = 0; }
+        int64_t p = pix[t];
+        if (p >= npix || p < -npix) { flag[1] = 1; p = 0; }
+        const int64_t q = p >= 0 ? p : npix + p;
+        key[t] = (((uint64_t)k * (uint64_t)npix + (uint64_t)q) << 1) | (p < 0 ? 1u : 0u);
+        val[t] = (int32_t)t;
+    }
+}
+
+__global__ void k_gr_heads(const uint64_t *__restrict__ skey, int64_t N, uint8_t *__restrict__ head)
+{
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x)
+        head[i] = (i == 0 || skey[i] != skey[i - 1]) ? 1 : 0;
+}
+
+// first read-back in one piece: entries, flags
+__global__ void k_gr_sizes(const int64_t *__restrict__ ne, const int32_t *__restrict__ flag, int64_t *__restrict__ out)
+{
+    if (threadIdx.x == 0) { out[0] = ne[0]; out[1] = flag[0]; out[2] = flag[1]; }
+}
+
+// Entry e = the sorted samples [estart[e], estart[e + 1]): its group, pixel id (negative for an
+// off-map read), ga_e = sum w a in sample order (the sort is stable), and its key for the
+// pixel-major sort (the pixel; npix for an unbinned entry, which sorts behind every row).
+__global__ void __launch_bounds__(256) k_gr_entries(const uint64_t *__restrict__ skey, const int32_t *__restrict__ sval,
+                                                    const int32_t *__restrict__ estart, int64_t ne, int64_t N,
+                                                    int64_t npix, const double *__restrict__ az,
+                                                    const double *__restrict__ w, const double *__restrict__ mu,
+                                                    const double *__restrict__ sigma, int32_t *__restrict__ egrp,
+                                                    int32_t *__restrict__ gpix, double *__restrict__ ga,
+                                                    int32_t *__restrict__ pkey, int32_t *__restrict__ pval)
+{
+    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < ne; e += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t i0 = estart[e], i1 = e + 1 < ne ? (int64_t)estart[e + 1] : N;
+        const uint64_t key = skey[i0];
+        const bool off = key & 1u;
+        const int64_t k = (int64_t)((key >> 1) / (uint64_t)npix), q = (int64_t)((key >> 1) % (uint64_t)npix);
+        const double m = mu[k], sg = sigma[k];
+        double acc = 0.0;
+        for (int64_t i = i0; i < i1; ++i) {
+            const int64_t t = sval[i];
+            const double a = sg > 0.0 ? (az[t] - m) / sg : 0.0;
+            acc += w[t] * a;
+        }
+        egrp[e] = (int32_t)k;
+        gpix[e] = (int32_t)(off ? q - npix : q);
+        ga[e] = acc;
+        pkey[e] = (int32_t)(off ? npix : q);
+        pval[e] = (int32_t)e;
+    }
+}
+
+// pixel-major copy of the binned entries (sorted position j < nnzb = row pointer of npix)
+__global__ void k_gr_pixel_entries(const int32_t *__restrict__ spkey, const int32_t *__restrict__ spval, int64_t ne,
+                                   int64_t npix, const int32_t *__restrict__ egrp, const double *__restrict__ ga,
+                                   int32_t *__restrict__ gpk, double *__restrict__ gpa)
+{
+    for (int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < ne; j += (int64_t)gridDim.x * blockDim.x) {
+        if (spkey[j] >= npix) continue;
+        const int32_t e = spval[j];
+        gpk[j] = egrp[e];
+        gpa[j] = ga[e];
+    }
+}
+
+// ---------------------------------------------------------------- per-iteration kernels
+// x'_i = x_i + c_{g(i)}
+__global__ void k_gr_fold(const double *__restrict__ x, const double *__restrict__ c, const int32_t *__restrict__ gint,
+                          int64_t NO, double *__restrict__ xp)
+{
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < NO; i += (int64_t)gridDim.x * blockDim.x)
+        xp[i] = x[i] + c[gint[i]];
+}
+
+// num_p += sum_{e in pixel row p} ga_e s_{k(e)}: a gather per pixel row, kBinLanes lanes per row
+// (lane-strided, then the lanes' sums); rows without entries are not written.
+__global__ void __launch_bounds__(256) k_gr_bin(const int64_t *__restrict__ gprow, const int32_t *__restrict__ gpk,
+                                                const double *__restrict__ gpa, const double *__restrict__ s,
+                                                int64_t npix, double *__restrict__ num)
+{
+    const int sub = threadIdx.x & (kBinLanes - 1);
+    const int64_t step = (int64_t)gridDim.x * blockDim.x / kBinLanes;
+    for (int64_t p = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kBinLanes; p < npix; p += step) {
+        const int64_t e0 = gprow[p], e1 = gprow[p + 1];
+        double acc = 0.0;
+        for (int64_t j = e0 + sub; j < e1; j += kBinLanes) acc = fma(gpa[j], s[gpk[j]], acc);
+#pragma unroll
+        for (int o = kBinLanes / 2; o > 0; o >>= 1) acc += __shfl_xor(acc, o, kBinLanes);
+        if (sub == 0 && e1 > e0) num[p] += acc;
+    }
+}
+
+// Chunk partials.  Workgroups [0, nce): sum of ga_e m[read pixel of e] over one chunk of a group
+// row, m = num / h on the fly; each thread keeps 4 entry loads then 4 map gathers in flight.
+// Workgroups [nce, nce + nco): one chunk of a group's offsets -- y_o += wa_o s_k (not for the
+// right-hand side, s == NULL), partials of sum y_o and of sum wa_o x'_o.
+__global__ void __launch_bounds__(256) k_gr_parts(const int64_t *__restrict__ chunks, int64_t nce,
+                                                  const int32_t *__restrict__ gpix, const double *__restrict__ ga,
+                                                  const double *__restrict__ num, const double *__restrict__ h,
+                                                  int64_t npix, const int32_t *__restrict__ glist,
+                                                  const double *__restrict__ wa, const double *__restrict__ xp,
+                                                  const double *__restrict__ s, double *__restrict__ y,
+                                                  double *__restrict__ part)
+{
+    __shared__ double red[4];
+    const int64_t c = blockIdx.x;
+    const int64_t k = chunks[3 * c], b = chunks[3 * c + 1], e = chunks[3 * c + 2];
+    if (c < nce) {
+        constexpr int U = 4;
+        double acc = 0.0;
+        for (int64_t j = b + threadIdx.x; j < e; j += 256 * U) {
+            int64_t q[U];
+            double a[U], m[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const bool in = j + u * 256 < e;
+                q[u] = in ? wrap_pixel(gpix[j + u * 256], npix) : 0;
+                a[u] = in ? ga[j + u * 256] : 0.0;
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) m[u] = map_value(num, h, q[u]);
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (j + u * 256 < e) acc = fma(a[u], m[u], acc);
+        }
+        acc = block_sum(acc, red);
+        if (threadIdx.x == 0) part[c] = acc;
+    } else {
+        const double sk = s ? s[k] : 0.0;
+        double acc1 = 0.0, acca = 0.0;
+        for (int64_t j = b + threadIdx.x; j < e; j += 256) {
+            const int64_t o = glist[j];
+            double yv = y[o];
+            if (s) {
+                const double wv = wa[o];
+                yv = fma(wv, sk, yv);
+                y[o] = yv;
+                acca = fma(wv, xp[o], acca);
+            }
+            acc1 += yv;
+        }
+        acc1 = block_sum(acc1, red);
+        acca = block_sum(acca, red);
+        if (threadIdx.x == 0) {
+            part[nce + 2 * (c - nce)] = acc1;
+            part[nce + 2 * (c - nce) + 1] = acca;
+        }
+    }
+}
+
+// One wave per group: its chunk partials added in a fixed order (lane-strided in chunk order,
+// then the wave).  z[k] = za_k (s == NULL: ba_k), z[K + k] = z1_k.
+__global__ void __launch_bounds__(64) k_gr_finish(const int64_t *__restrict__ cgrp, int64_t K, int64_t nce,
+                                                  const double *__restrict__ part, const double *__restrict__ saa,
+                                                  const double *__restrict__ ta, const double *__restrict__ s,
+                                                  double *__restrict__ z)
+{
+    const int64_t k = blockIdx.x;
+    double ae = 0.0, a1 = 0.0, aa = 0.0;
+    for (int64_t c = cgrp[k] + threadIdx.x; c < cgrp[k + 1]; c += 64) ae += part[c];
+    for (int64_t c = cgrp[K + 1 + k] + threadIdx.x; c < cgrp[K + 2 + k]; c += 64) {
+        a1 += part[nce + 2 * c];
+        aa += part[nce + 2 * c + 1];
+    }
+    ae = wave_sum(ae);
+    a1 = wave_sum(a1);
+    aa = wave_sum(aa);
+    if (threadIdx.x == 0) {
+        z[k] = s ? (aa + saa[k] * s[k]) - ae : ta[k] - ae;
+        z[K + k] = a1;
+    }
+}
+
+// The CG's vector algebra on the 2K-value tails (s | c), one workgroup each; the offsets' part of
+// every vector runs through the plain problem's kernels.  Sums are fixed-order.
+// out += a . b
+__global__ void __launch_bounds__(256) k_gr_tail_dot(const double *__restrict__ a, const double *__restrict__ b,
+                                                     int64_t n, double *__restrict__ out)
+{
+    __shared__ double red[4];
+    double acc = 0.0;
+    for (int64_t i = threadIdx.x; i < n; i += 256) acc = fma(a[i], b[i], acc);
+    acc = block_sum(acc, red);
+    if (threadIdx.x == 0) out[0] += acc;
+}
+
+// alpha = rr / pq; x += alpha p; r -= alpha q; rr_new += r . r (rr_new holds the offsets' part)
+__global__ void __launch_bounds__(256) k_gr_tail_update(const double *__restrict__ rr, const double *__restrict__ pq,
+                                                        double *__restrict__ x, double *__restrict__ r,
+                                                        const double *__restrict__ p, const double *__restrict__ q,
+                                                        int64_t n, double *__restrict__ rr_new)
+{
+    __shared__ double red[4];
+    const double alpha = rr[0] / pq[0];
+    double acc = 0.0;
+    for (int64_t i = threadIdx.x; i < n; i += 256) {
+        x[i] += alpha * p[i];
+        const double rv = r[i] - alpha * q[i];
+        r[i] = rv;
+        acc = fma(rv, rv, acc);
+    }
+    acc = block_sum(acc, red);
+    if (threadIdx.x == 0) rr_new[0] += acc;
+}
+
+// p = r + (rr_new / rr) p
+__global__ void __launch_bounds__(256) k_gr_tail_direction(const double *__restrict__ rr_new,
+                                                           const double *__restrict__ rr, double *__restrict__ p,
+                                                           const double *__restrict__ r, int64_t n)
+{
+    const double beta = rr_new[0] / rr[0];
+    for (int64_t i = threadIdx.x; i < n; i += 256) p[i] = r[i] + beta * p[i];
+}
+
+void ground_free(comap_ground *g, bool idle)
+{
+    void *b[] = {g->gint, g->glist, g->wa, g->mu, g->sigma, g->saa, g->ta, g->gpix, g->ga, g->gprow, g->gpk, g->gpa,
+                 g->chunks, g->cgrp, g->part};
+    comap_tmp_free_on(b, (int)(sizeof(b) / sizeof(b[0])), nullptr, idle);
+    delete g;
+}
+
+int ground_build(comap_ground *g, const int32_t *pix, const double *az, const double *tod, const double *w,
+                 const int32_t *gid)
+{
+    comap_destriper *d = g->d;
+    comap_ctx *ctx = g->ctx;
+    hipStream_t st = ctx->stream;
+    const int64_t N = d->N, NO = d->NO, npix = d->npix, K = g->K;
+    const int L = d->L;
+    int rc = 0;
+    rc |= dalloc(ctx, &g->gint, NO);
+    rc |= dalloc(ctx, &g->glist, NO);
+    rc |= dalloc(ctx, &g->wa, NO);
+    rc |= dalloc(ctx, &g->mu, K);
+    rc |= dalloc(ctx, &g->sigma, K);
+    rc |= dalloc(ctx, &g->saa, K);
+    rc |= dalloc(ctx, &g->ta, K);
+    rc |= dalloc(ctx, &g->gprow, npix + 1);
+    rc |= dalloc(ctx, &g->cgrp, 2 * (K + 1));
+    if (rc) return -2;
+
+    DevTemps tmp(st);
+    const int64_t nmax = std::max<int64_t>(N, std::max<int64_t>(NO, K + 1));
+    uint64_t *key = nullptr, *skey = nullptr;
+    int32_t *val = nullptr, *sval = nullptr, *estart = nullptr, *gs = nullptr, *flag = nullptr;
+    uint8_t *head = nullptr;
+    double *ov = nullptr, *gv = nullptr;
+    int64_t *grow = nullptr, *garow = nullptr, *cnt = nullptr;
+    COMAP_CHECK(ctx, tmp.alloc(&key, N));
+    COMAP_CHECK(ctx, tmp.alloc(&skey, N));
+    COMAP_CHECK(ctx, tmp.alloc(&val, nmax));
+    COMAP_CHECK(ctx, tmp.alloc(&sval, nmax));
+    COMAP_CHECK(ctx, tmp.alloc(&estart, N));
+    COMAP_CHECK(ctx, tmp.alloc(&gs, NO));
+    COMAP_CHECK(ctx, tmp.alloc(&flag, 2));
+    COMAP_CHECK(ctx, tmp.alloc(&head, N));
+    COMAP_CHECK(ctx, tmp.alloc(&ov, 3 * NO));
+    COMAP_CHECK(ctx, tmp.alloc(&gv, 3 * K));
+    COMAP_CHECK(ctx, tmp.alloc(&grow, K + 1));
+    COMAP_CHECK(ctx, tmp.alloc(&garow, K + 1));
+    COMAP_CHECK(ctx, tmp.alloc(&cnt, 4));
+    const int kbits = bits_for((uint64_t)K), pbits = bits_for((uint64_t)npix + 1);
+    const int sbits = bits_for((uint64_t)K * (uint64_t)npix * 2u);
+    // sort scratch: the largest of the three sorts (the last one's size is bounded by N) and the select
+    size_t tb = 0, b1 = 0;
+    COMAP_CHECK(ctx, rocprim::radix_sort_pairs(nullptr, b1, key, skey, val, sval, (size_t)N, 0u, (unsigned)sbits, st));
+    tb = std::max(tb, b1);
+    COMAP_CHECK(ctx, rocprim::radix_sort_pairs(nullptr, b1, val, sval, val, sval, (size_t)NO, 0u, (unsigned)kbits, st));
+    tb = std::max(tb, b1);
+    COMAP_CHECK(ctx, rocprim::radix_sort_pairs(nullptr, b1, val, sval, val, sval, (size_t)N, 0u, (unsigned)pbits, st));
+    tb = std::max(tb, b1);
+    COMAP_CHECK(ctx, rocprim::radix_sort_pairs(nullptr, b1, val, sval, val, sval, (size_t)nmax, 0u, 32u, st));
+    tb = std::max(tb, b1);
+    hipcub::CountingInputIterator<int32_t> iota(0);
+    COMAP_CHECK(ctx, hipcub::DeviceSelect::Flagged(nullptr, b1, iota, head, estart, cnt, (int)N, st));
+    tb = std::max(tb, b1);
+    char *cub = nullptr;
+    COMAP_CHECK(ctx, tmp.alloc(&cub, tb));
+
+    // ---- 1. the offsets' groups in the internal order, and each group's offset list
+    COMAP_CHECK(ctx, hipMemsetAsync(flag, 0, 8, st));
+    k_gr_gint<<<grid_for(NO), 256, 0, st>>>(gid, d->perm, NO, K, g->gint, val, flag);
+    COMAP_LAUNCH_CHECK(ctx);
+    b1 = tb;
+    COMAP_CHECK(ctx, rocprim::radix_sort_pairs(cub, b1, g->gint, gs, val, g->glist, (size_t)NO, 0u, (unsigned)kbits, st));
+    k_gr_rowptr<<<grid_for(K + 1), 256, 0, st>>>(gs, NO, K, grow);
+    COMAP_LAUNCH_CHECK(ctx);
+
+    // ---- 2. mu, sigma per group; wa per offset; Saa, Ta per group
+    double *o0 = ov, *o1 = ov + NO, *o2 = ov + 2 * NO;
+    k_gr_offsets<0><<<grid_for(NO), 256, 0, st>>>(az, w, tod, d->perm, g->gint, nullptr, nullptr, NO, L, o0, o1, o2);
+    k_gr_group<0><<<(unsigned)K, 256, 0, st>>>(o0, g->glist, grow, gv);
+    k_gr_group<1><<<(unsigned)K, 256, 0, st>>>(o1, g->glist, grow, gv + K);
+    k_gr_group<2><<<(unsigned)K, 256, 0, st>>>(o2, g->glist, grow, gv + 2 * K);
+    k_gr_mean<<<grid_for(K), 256, 0, st>>>(gv, grow, K, L, g->mu);
+    k_gr_offsets<1><<<grid_for(NO), 256, 0, st>>>(az, w, tod, d->perm, g->gint, g->mu, nullptr, NO, L, o0, o1, o2);
+    k_gr_group<0><<<(unsigned)K, 256, 0, st>>>(o0, g->glist, grow, gv);
+    k_gr_rms<<<grid_for(K), 256, 0, st>>>(gv, gv + K, gv + 2 * K, grow, K, L, g->sigma);
+    k_gr_offsets<2><<<grid_for(NO), 256, 0, st>>>(az, w, tod, d->perm, g->gint, g->mu, g->sigma, NO, L, g->wa, o1, o2);
+    k_gr_group<0><<<(unsigned)K, 256, 0, st>>>(o1, g->glist, grow, g->saa);
+    k_gr_group<0><<<(unsigned)K, 256, 0, st>>>(o2, g->glist, grow, g->ta);
+    COMAP_LAUNCH_CHECK(ctx);
+
+    // ---- 3. the samples sorted by (group, read pixel, off-map); one entry per distinct key
+    k_gr_keys<<<grid_for(N, 65536), 256, 0, st>>>(pix, gid, N, L, npix, K, key, val, flag);
+    COMAP_LAUNCH_CHECK(ctx);
+    b1 = tb;
+    COMAP_CHECK(ctx, rocprim::radix_sort_pairs(cub, b1, key, skey, val, sval, (size_t)N, 0u, (unsigned)sbits, st));
+    k_gr_heads<<<grid_for(N, 65536), 256, 0, st>>>(skey, N, head);
+    COMAP_LAUNCH_CHECK(ctx);
+    b1 = tb;
+    COMAP_CHECK(ctx, hipcub::DeviceSelect::Flagged(cub, b1, iota, head, estart, cnt, (int)N, st));
+    k_gr_sizes<<<1, 64, 0, st>>>(cnt, flag, cnt + 1);
+    COMAP_LAUNCH_CHECK(ctx);
+    int64_t hw[3] = {0, 0, 0};
+    COMAP_CHECK(ctx, hipMemcpyAsync(hw, cnt + 1, sizeof(hw), hipMemcpyDeviceToHost, st));
+    COMAP_CHECK(ctx, hipStreamSynchronize(st));
+    if (hw[1]) return comap_fail(ctx, -3, "ground group id out of range (valid: 0 .. n_groups - 1)");
+    if (hw[2]) return comap_fail(ctx, -3, "pixel index out of range for the map (>= npix or < -npix)");
+    const int64_t ne = hw[0];
+    if (ne < 1 || ne > N) return comap_fail(ctx, -2, "ground set-up: bad entry count");
+    g->nnz = ne;
+
+    // ---- 4. the group-major entries, then their pixel-major copy
+    int32_t *egrp = nullptr, *pkey = nullptr, *spkey = nullptr;
+    rc |= dalloc(ctx, &g->gpix, ne);
+    rc |= dalloc(ctx, &g->ga, ne);
+    rc |= dalloc(ctx, &g->gpk, ne);        // nnzb <= nnz
+    rc |= dalloc(ctx, &g->gpa, ne);
+    if (rc) return -2;
+    COMAP_CHECK(ctx, tmp.alloc(&egrp, ne));
+    COMAP_CHECK(ctx, tmp.alloc(&pkey, ne));
+    COMAP_CHECK(ctx, tmp.alloc(&spkey, ne));
+    // (val / sval are free again: the pixel-major sort's values)
+    k_gr_entries<<<grid_for(ne, 65536), 256, 0, st>>>(skey, sval, estart, ne, N, npix, az, w, g->mu, g->sigma, egrp,
+                                                      g->gpix, g->ga, pkey, val);
+    k_gr_rowptr<<<grid_for(K + 1), 256, 0, st>>>(egrp, ne, K, garow);
+    COMAP_LAUNCH_CHECK(ctx);
+    int32_t *spval = estart;               // (the segment starts are consumed)
+    COMAP_CHECK(ctx, rocprim::radix_sort_pairs(nullptr, b1, pkey, spkey, val, spval, (size_t)ne, 0u, (unsigned)pbits, st));
+    if (b1 > tb) {
+        tb = b1;
+        COMAP_CHECK(ctx, tmp.alloc(&cub, tb));
+    }
+    b1 = tb;
+    COMAP_CHECK(ctx, rocprim::radix_sort_pairs(cub, b1, pkey, spkey, val, spval, (size_t)ne, 0u, (unsigned)pbits, st));
+    k_gr_rowptr<<<grid_for(npix + 1), 256, 0, st>>>(spkey, ne, npix, g->gprow);
+    k_gr_pixel_entries<<<grid_for(ne, 65536), 256, 0, st>>>(spkey, spval, ne, npix, egrp, g->ga, g->gpk, g->gpa);
+    COMAP_LAUNCH_CHECK(ctx);
+
+    // ---- 5. read-back 2: the groups' row bounds; the reduction chunks
+    std::vector<int64_t> hrow(2 * (K + 1) + 1);
+    COMAP_CHECK(ctx, hipMemcpyAsync(hrow.data(), garow, 8 * (size_t)(K + 1), hipMemcpyDeviceToHost, st));
+    COMAP_CHECK(ctx, hipMemcpyAsync(hrow.data() + K + 1, grow, 8 * (size_t)(K + 1), hipMemcpyDeviceToHost, st));
+    COMAP_CHECK(ctx, hipMemcpyAsync(hrow.data() + 2 * (K + 1), g->gprow + npix, 8, hipMemcpyDeviceToHost, st));
+    COMAP_CHECK(ctx, hipStreamSynchronize(st));
+    g->nnzb = hrow[2 * (K + 1)];
+    if (hrow[K] != ne || hrow[2 * K + 1] != NO || g->nnzb < 0 || g->nnzb > ne)
+        return comap_fail(ctx, -2, "ground set-up: inconsistent row bounds");
+    std::vector<int64_t> ch, cg(2 * (K + 1));
+    for (int pass = 0; pass < 2; ++pass) {
+        const int64_t *row = hrow.data() + pass * (K + 1);
+        const int64_t step = pass ? kChunkO : kChunkE;
+        int64_t n = 0;
+        for (int64_t k = 0; k < K; ++k) {
+            cg[pass * (K + 1) + k] = n;
+            for (int64_t b = row[k]; b < row[k + 1]; b += step, ++n) {
+                ch.push_back(k);
+                ch.push_back(b);
+                ch.push_back(std::min(b + step, row[k + 1]));
+            }
+        }
+        cg[pass * (K + 1) + K] = n;
+        (pass ? g->nco : g->nce) = n;
+    }
+    const int64_t nc = g->nce + g->nco;
+    rc |= dalloc(ctx, &g->chunks, 3 * nc);
+    rc |= dalloc(ctx, &g->part, g->nce + 2 * g->nco);
+    if (rc) return -2;
+    COMAP_CHECK(ctx, comap_upload(g->chunks, ch.data(), 8 * ch.size(), st));
+    COMAP_CHECK(ctx, comap_upload(g->cgrp, cg.data(), 8 * cg.size(), st));
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int comap_destripe_ground_create(comap_destriper *d, const int32_t *pix, const double *az, const double *tod,
+                                            const double *w, const int32_t *gid, int64_t n_groups, comap_ground **out)
+{
+    if (!d || !out) return -1;
+    comap_ctx *ctx = d->ctx;
+    if (!pix || !az || !tod || !w || !gid) return comap_fail(ctx, -1, "ground template: null input");
+    if (d->nb != 1) return comap_fail(ctx, -1, "ground template: one band per problem (batched bands are not supported)");
+    if (n_groups < 1 || n_groups > (1 << 24)) return comap_fail(ctx, -1, "ground template: 1 .. 2^24 groups");
+    if (d->N >= (int64_t(1) << 31) || d->npix >= (int64_t(1) << 31) - 1)
+        return comap_fail(ctx, -1, "ground template: sample and pixel counts must fit 31 bits");
+    if ((uint64_t)n_groups * (uint64_t)d->npix >= (uint64_t(1) << 62))
+        return comap_fail(ctx, -1, "ground template: groups x pixels must fit 62 bits");
+    COMAP_DEVICE_GUARD(ctx);
+    comap_ground *g = new comap_ground;
+    g->d = d;
+    g->ctx = ctx;
+    g->NO = d->NO;
+    g->npix = d->npix;
+    g->K = n_groups;
+    const int rc = ground_build(g, pix, az, tod, w, gid);
+    if (rc) {
+        (void)hipStreamSynchronize(ctx->stream);
+        ground_free(g, true);
+        return rc;
+    }
+    *out = g;
+    return 0;
+}
+
+extern "C" int comap_destripe_ground_destroy(comap_ground *g)
+{
+    if (!g) return 0;
+    COMAP_DEVICE_GUARD(g->ctx);
+    (void)hipDeviceSynchronize();
+    ground_free(g, true);
+    return 0;
+}
+
+extern "C" int64_t comap_destripe_ground_n_groups(const comap_ground *g) { return g ? g->K : -1; }
+
+extern "C" int comap_destripe_ground_nnz(const comap_ground *g, int64_t *nnz_group_major, int64_t *nnz_pixel_major)
+{
+    if (!g) return -1;
+    if (nnz_group_major) *nnz_group_major = g->nnz;
+    if (nnz_pixel_major) *nnz_pixel_major = g->nnzb;
+    return 0;
+}
+
+extern "C" int comap_destripe_ground_stats(comap_ground *g, double *mu, double *sigma)
+{
+    if (!g) return -1;
+    COMAP_DEVICE_GUARD(g->ctx);
+    comap_ctx *ctx = g->ctx;
+    const size_t b = 8 * (size_t)g->K;
+    if (mu) COMAP_CHECK(ctx, hipMemcpyAsync(mu, g->mu, b, hipMemcpyDeviceToDevice, ctx->stream));
+    if (sigma) COMAP_CHECK(ctx, hipMemcpyAsync(sigma, g->sigma, b, hipMemcpyDeviceToDevice, ctx->stream));
+    return 0;
+}
+
+extern "C" int comap_destripe_ground_fold(comap_ground *g, const double *x, const double *c, double *xprime)
+{
+    if (!g || !x || !c || !xprime) return -1;
+    COMAP_DEVICE_GUARD(g->ctx);
+    comap_ctx *ctx = g->ctx;
+    k_gr_fold<<<grid_for(g->NO), 256, 0, ctx->stream>>>(x, c, g->gint, g->NO, xprime);
+    COMAP_LAUNCH_CHECK(ctx);
+    return 0;
+}
+
+extern "C" int comap_destripe_ground_bin(comap_ground *g, const double *s, double *num)
+{
+    if (!g || !s || !num) return -1;
+    COMAP_DEVICE_GUARD(g->ctx);
+    comap_ctx *ctx = g->ctx;
+    k_gr_bin<<<grid_for(g->npix * kBinLanes, 65536), 256, 0, ctx->stream>>>(g->gprow, g->gpk, g->gpa, s, g->npix, num);
+    COMAP_LAUNCH_CHECK(ctx);
+    return 0;
+}
+
+static int ground_project(comap_ground *g, const double *xprime, const double *s, const double *num, const double *h,
+                          double *y, double *z)
+{
+    COMAP_DEVICE_GUARD(g->ctx);
+    comap_ctx *ctx = g->ctx;
+    const int64_t nc = g->nce + g->nco;
+    if (nc)
+        k_gr_parts<<<(unsigned)nc, 256, 0, ctx->stream>>>(g->chunks, g->nce, g->gpix, g->ga, num, h ? h : g->d->h,
+                                                          g->npix, g->glist, g->wa, xprime, s, y, g->part);
+    k_gr_finish<<<(unsigned)g->K, 64, 0, ctx->stream>>>(g->cgrp, g->K, g->nce, g->part, g->saa, g->ta, s, z);
+    COMAP_LAUNCH_CHECK(ctx);
+    return 0;
+}
+
+extern "C" int comap_destripe_ground_project(comap_ground *g, const double *xprime, const double *s, const double *num,
+                                             const double *h, double *y, double *z)
+{
+    if (!g || !xprime || !s || !num || !y || !z) return -1;
+    return ground_project(g, xprime, s, num, h, y, z);
+}
+
+extern "C" int comap_destripe_ground_rhs(comap_ground *g, const double *num, const double *h, const double *b, double *z)
+{
+    if (!g || !num || !b || !z) return -1;
+    // (the right-hand side reads b and leaves it as it is)
+    return ground_project(g, nullptr, nullptr, num, h, const_cast<double *>(b), z);
+}
+
+extern "C" int comap_destripe_ground_tail_dot(comap_ground *g, const double *a, const double *b, double *dot)
+{
+    if (!g || !a || !b || !dot) return -1;
+    COMAP_DEVICE_GUARD(g->ctx);
+    comap_ctx *ctx = g->ctx;
+    k_gr_tail_dot<<<1, 256, 0, ctx->stream>>>(a, b, 2 * g->K, dot);
+    COMAP_LAUNCH_CHECK(ctx);
+    return 0;
+}
+
+extern "C" int comap_destripe_ground_tail_update(comap_ground *g, const double *rr, const double *pq, double *x,
+                                                 double *r, const double *p, const double *q, double *rr_new)
+{
+    if (!g || !rr || !pq || !x || !r || !p || !q || !rr_new) return -1;
+    COMAP_DEVICE_GUARD(g->ctx);
+    comap_ctx *ctx = g->ctx;
+    k_gr_tail_update<<<1, 256, 0, ctx->stream>>>(rr, pq, x, r, p, q, 2 * g->K, rr_new);
+    COMAP_LAUNCH_CHECK(ctx);
+    return 0;
+}
+
+extern "C" int comap_destripe_ground_tail_direction(comap_ground *g, const double *rr_new, const double *rr, double *p,
+                                                    const double *r)
+{
+    if (!g || !rr_new || !rr || !p || !r) return -1;
+    COMAP_DEVICE_GUARD(g->ctx);
+    comap_ctx *ctx = g->ctx;
+    k_gr_tail_direction<<<1, 256, 0, ctx->stream>>>(rr_new, rr, p, r, 2 * g->K);
+    COMAP_LAUNCH_CHECK(ctx);
+    return 0;
+}

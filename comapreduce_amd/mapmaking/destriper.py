@@ -519,6 +519,180 @@ class DeviceOps:
         return x, [int(v) for v in it][:nbo], maps
 
 
+def ground_groups(feedid, obsids, offset_length):
+    """Ground-template group of every offset: (gid int32 [N/L], unique_obsids, unique_feeds).
+
+    Group k = i * n_feeds + j for observation i of np.unique(obsids) and feed j of
+    np.unique(feedid), the reference's order (op_Ax_with_ground, Destriper.py:279-287); a
+    combination without samples is simply a group no offset belongs to.  The device operator
+    works on whole offsets, so every offset must lie in one group (read_comap_data keeps
+    floor(n / L) * L samples per feed and scan, which guarantees it): ValueError otherwise,
+    and when the lengths disagree or are no multiple of offset_length."""
+    feedid, obsids = np.asarray(feedid).reshape(-1), np.asarray(obsids).reshape(-1)
+    L = int(offset_length)
+    if feedid.size != obsids.size:
+        raise ValueError(f'feedid ({feedid.size}) and obsids ({obsids.size}) must have the same length')
+    if L < 1 or feedid.size % L:
+        raise ValueError(f'{feedid.size} samples are not a multiple of offset_length {L}')
+    uobs, iobs = np.unique(obsids, return_inverse=True)
+    ufeed, ifeed = np.unique(feedid, return_inverse=True)
+    gid = (iobs.reshape(-1) * ufeed.size + ifeed.reshape(-1)).reshape(-1, L)
+    if gid.size and np.any(gid != gid[:, :1]):
+        bad = int(np.nonzero(np.any(gid != gid[:, :1], axis=1))[0][0])
+        raise ValueError(f'offset {bad} straddles two (observation, feed) groups: the ground template needs '
+                         'every offset inside one group')
+    return gid[:, 0].astype(np.int32), uobs, ufeed
+
+
+class GroundOps:
+    """The destriper operator with a ground (azimuth) template per (observation, feed):
+    the reference's op_Ax_with_ground (Destriper.py:265-336) as the operator object that
+    ``cg_solve`` drives (comap_destripe_ground_* around a DeviceOps' own calls).
+
+    Vectors hold [x (N/L offsets, internal order) | s (K slopes) | c (K levels)], groups in
+    ``ground_groups`` order.  The azimuth enters centred and scaled per group, a = (az -
+    mu_k) / sigma_k (0 for a constant azimuth) -- see ``fit`` for the reference's units.  The
+    offsets' part of every vector runs through the plain problem's kernels, the 2K-value
+    tails through comap_destripe_ground_tail_* (no host synchronisation)."""
+
+    def __init__(self, ops, az, gid, n_groups):
+        torch = ops.torch
+        if ops.nb != 1:
+            raise NotImplementedError('the ground template solves one band (batched bands are not supported)')
+        self.ops, self.torch, self.dev, self.ctx = ops, torch, ops.dev, ops.ctx
+        self.K, self.NO, self.npix = int(n_groups), ops.n_offsets, ops.npix
+        self.n_offsets = self.NO + 2 * self.K
+        az = ops._t(az, torch.float64)
+        gid = ops._t(gid, torch.int32)
+        if az.numel() != ops.pix.numel():
+            raise ValueError('az must have one value per sample')
+        if gid.numel() != self.NO:
+            raise ValueError('one ground group id per offset')
+        g = ctypes.c_void_p()
+        N.bind_stream(self.ctx, self.dev)
+        rc = N.lib().comap_destripe_ground_create(ops.h, N.dptr(ops.pix), N.dptr(az), N.dptr(ops.tod), N.dptr(ops.w),
+                                                  N.dptr(gid), self.K, ctypes.byref(g))
+        if rc == -3:
+            raise IndexError(f'ground template: {N.lib().comap_last_error(self.ctx).decode()}')
+        N.check(rc, self.ctx, 'comap_destripe_ground_create')
+        self.g = g
+        self.xp = ops.zeros(self.NO)                 # x' = x + c[g(o)], the level folded into the offsets
+        self._folded = None                          # (vector, its version) xp was folded from by bin()
+        self.mu, self.sigma = ops.zeros(self.K), ops.zeros(self.K)
+        self._c('comap_destripe_ground_stats', self.g, N.dptr(self.mu), N.dptr(self.sigma))
+
+    def __del__(self):
+        try:
+            if getattr(self, 'g', None) is not None:
+                self.torch.cuda.synchronize(self.dev)
+                N.lib().comap_destripe_ground_destroy(self.g)
+                self.g = None
+        except Exception:  # pragma: no cover
+            pass
+
+    def _c(self, fn, *args):
+        self.ops._c(fn, *args)
+
+    def nnz(self):
+        """(group, pixel) entries: (group-major incl. off-map reads, pixel-major binned only)."""
+        a, b = ctypes.c_int64(), ctypes.c_int64()
+        N.lib().comap_destripe_ground_nnz(self.g, ctypes.byref(a), ctypes.byref(b))
+        return int(a.value), int(b.value)
+
+    # ---- vector helpers (cg_solve's protocol)
+    def zeros(self, n):
+        return self.ops.zeros(n)
+
+    def scalar(self):
+        return self.ops.zeros(1)
+
+    def copy(self, a):
+        return a.clone()
+
+    def host_scalar(self, s):
+        return float(s.item())
+
+    def set_scalar(self, dst, src):
+        dst.copy_(src)
+
+    def local_maps(self):
+        return self.ops.local_maps()
+
+    def _u(self, t):
+        if t.numel() != self.n_offsets or t.dtype != self.torch.float64 or not t.is_contiguous():
+            raise ValueError(f'ground vector must be contiguous float64 with {self.n_offsets} values')
+        return t
+
+    def split(self, u):
+        """(x [N/L] internal order, s [K], c [K]) views of a vector."""
+        u = self._u(u)
+        return u[:self.NO], u[self.NO:self.NO + self.K], u[self.NO + self.K:]
+
+    def _fold(self, u, reuse=False):
+        """x' for vector u into self.xp; returns u's slopes.  reuse: project(u) right after
+        bin(u), as cg_solve calls them, keeps bin's x' (every call here that writes a vector
+        forgets it: the native kernels write behind torch's version counter)."""
+        x, s, c = self.split(u)
+        f = self._folded
+        if not (reuse and f is not None and f[0] is u and f[1] == u._version):
+            self._c('comap_destripe_ground_fold', self.g, N.dptr(x), N.dptr(c), N.dptr(self.xp))
+        self._folded = (u, u._version)
+        return s
+
+    def _tail(self, t):
+        return N.dptr(self._u(t)[self.NO:])
+
+    # ---- operator pieces
+    def bin(self, u, mode, out):
+        """mode 0: num = [W F | W G] u; mode 1: the destriped map's numerator, naive - that."""
+        s = self._fold(u)
+        self.ops.bin(self.xp, mode, out)
+        self._c('comap_destripe_ground_bin', self.g, N.dptr(s if mode == 0 else -s), self.ops._m(out))
+
+    def project(self, u, num, h, y, dot=None):
+        y = self._u(y)
+        if u is None:                                 # b: the offsets' rows, then the tail from them
+            self._folded = None
+            self.ops.project(None, num, h, y)
+            self._c('comap_destripe_ground_rhs', self.g, self.ops._m(num), self.ops._m(h), N.dptr(y), self._tail(y))
+            return
+        s = self._fold(u, reuse=True)
+        self._folded = None
+        self.ops.project(self.xp, num, h, y)
+        self._c('comap_destripe_ground_project', self.g, N.dptr(self.xp), N.dptr(s), self.ops._m(num), self.ops._m(h),
+                N.dptr(y), self._tail(y))
+        if dot is not None:
+            self.dot(u, y, dot)
+
+    def dot(self, a, b, out):
+        self.ops.dot(self._u(a), self._u(b), out)
+        self._c('comap_destripe_ground_tail_dot', self.g, self._tail(a), self._tail(b), self.ops._s(out))
+
+    def cg_update(self, rr, pq, x, r, p, q, rr_new):
+        self._folded = None
+        self.ops.cg_update(rr, pq, self._u(x), self._u(r), self._u(p), self._u(q), rr_new)
+        self._c('comap_destripe_ground_tail_update', self.g, self.ops._s(rr), self.ops._s(pq), self._tail(x),
+                self._tail(r), self._tail(p), self._tail(q), self.ops._s(rr_new))
+
+    def cg_direction(self, rr_new, rr, p, r):
+        self._folded = None
+        self.ops.cg_direction(rr_new, rr, self._u(p), self._u(r))
+        self._c('comap_destripe_ground_tail_direction', self.g, self.ops._s(rr_new), self.ops._s(rr), self._tail(p),
+                self._tail(r))
+
+    # ---- results
+    def fit(self, u):
+        """(slope [K], level [K]) in the reference's units (per degree of raw azimuth):
+        slope = s / sigma, level = c - s mu / sigma (slope 0 where sigma == 0).  The level is
+        defined only up to the offsets' null space: a constant moved between c_k and the
+        group's offsets changes no residual, and CG from 0 returns the minimum-norm split."""
+        _, s, c = self.split(u)
+        torch = self.torch
+        slope = torch.where(self.sigma > 0, s / torch.where(self.sigma > 0, self.sigma, torch.ones_like(self.sigma)),
+                            torch.zeros_like(s))
+        return slope, c - slope * self.mu
+
+
 _COPY_STREAMS = {}
 
 
@@ -582,11 +756,17 @@ class DeviceDestriper:
     sharded).  The default is COMAP_DS_RANKS=shard until a multi-GPU run replaces the
     model's assumed all-reduce latency and bandwidth; gather forces the other."""
 
-    def __init__(self, pixels, tod, weights, offset_length, npix, device=None, keep=None, map_shape=None):
+    def __init__(self, pixels, tod, weights, offset_length, npix, device=None, keep=None, map_shape=None,
+                 ground=None):
         """map_shape (ny, nx): the map's row-major layout (CAR / WCS maps), when known; the
         operator then runs on a 2-D tiled internal pixel order (tiled_layout) and the maps
-        come back in the caller's order."""
+        come back in the caller's order.
+        ground (az, feedid, obsids), per sample: also fit an azimuth slope and a level per
+        (observation, feed) jointly with the offsets (GroundOps; the reference's
+        op_Ax_with_ground, Destriper.py:265-336).  solve() then adds res['ground'].  The fit is
+        per file and feed, hence local to a rank: one band on one rank only."""
         self.layout, self.okey = None, None
+        self.ground = None
         T = int(os.environ.get('COMAP_DS_TILE', str(TILE)))
         if T > 0 and T & (T - 1):
             # the Morton code inside a tile interleaves log2(T) bits: for another T it would
@@ -601,6 +781,11 @@ class DeviceDestriper:
         self.multi = np.ndim(tod) == 2 if not hasattr(tod, 'dim') else tod.dim() == 2
         self.gathered, self.plan = None, None
         d = _dist()
+        if ground is not None:
+            if self.multi:
+                raise NotImplementedError('the ground template solves one band: pass a 1-D tod')
+            if d is not None and d.get_world_size() > 1:
+                raise NotImplementedError('the ground template is not wired across ranks (sharded or gathered)')
         if d is not None and d.get_world_size() > 1:
             if self._choose_gather(d, pixels, tod, offset_length):
                 self._gather(d, pixels, tod, weights, keep, offset_length, npix, device)
@@ -608,6 +793,11 @@ class DeviceDestriper:
             if os.environ.get('COMAP_DS_COMPACT', '1') != '0':
                 pixels, npix = self._compact(pixels, int(npix), device)
         self.ops = N.retry_oom(DeviceOps, pixels, tod, weights, offset_length, npix, device, keep, self.okey)
+        if ground is not None:
+            az, feedid, obsids = ground
+            gid, uobs, ufeed = ground_groups(feedid, obsids, offset_length)
+            self.gops = N.retry_oom(GroundOps, self.ops, az, gid, uobs.size * ufeed.size)
+            self.ground = (uobs, ufeed)
 
     # ---- rank policy
     def _choose_gather(self, d, pixels, tod, offset_length):
@@ -788,6 +978,8 @@ class DeviceDestriper:
         rank solving alone overlaps their copy with the CG (solve_native_host).
         allreduce: the sharded CG's sum across ranks (default torch_allreduce; bench.py
         passes a TimedAllreduce to measure the per-iteration collective cost)."""
+        if self.ground is not None:
+            return self._solve_ground(threshold, niter, to_host)
         d = _dist()
         ops = self.ops
         if to_host and self.gathered is None and (d is None or d.get_world_size() == 1):
@@ -845,6 +1037,28 @@ class DeviceDestriper:
         return {'x': split(x), 'iters': it, 'maps': maps}
 
 
+    def _solve_ground(self, threshold, niter, to_host):
+        """solve() with the ground template: the eager ``cg_solve`` on GroundOps, then the maps
+        from the offsets AND the fitted templates.  Adds 'ground': {'obsids', 'feeds', 'slope',
+        'level'} (host arrays [n_obs, n_feeds], GroundOps.fit's units); 'x' holds the offsets."""
+        ops, g = self.ops, self.gops
+        u, it, h, nnum = cg_solve(g, lambda t: t, threshold, niter)
+        _, hits, _ = ops.local_maps()
+        num = ops.zeros(ops.npix)
+        g.bin(u, 1, num)
+        maps = {'map': ops.zeros(ops.npix), 'naive': ops.zeros(ops.npix), 'weight': h, 'hits': hits}
+        ops.div_map(num, h, maps['map'])
+        ops.div_map(nnum, h, maps['naive'])
+        if self.layout is not None:
+            maps = {k: self._untile(v, 1) for k, v in maps.items()}
+        maps['map2'] = maps['weight']
+        uobs, ufeed = self.ground
+        slope, level = (v.cpu().numpy().reshape(uobs.size, ufeed.size) for v in g.fit(u))
+        # ('solution': the whole CG vector [x internal order | s | c], GroundOps' units)
+        return {'x': ops.natural(u), 'iters': it, 'maps': maps_to_host(maps) if to_host else maps,
+                'ground': {'obsids': uobs, 'feeds': ufeed, 'slope': slope, 'level': level}, 'solution': u}
+
+
 def maps_to_host(maps):
     """{name: device tensor} -> {name: NumPy array}: one device-side stack and one copy
     into page-locked host memory from the library's cache (a pageable copy per map runs
@@ -862,19 +1076,31 @@ def maps_to_host(maps):
 
 def run_destriper(_pointing, _tod, _weights, offset_length, pixel_edges, az=None, el=None, ra=None, dec=None,
                   feedid=None, obsids=None, obsid_cuts=None, threshold=1e-6, niter=100, chi2_cutoff=100,
-                  special_weight=None, healpix=False, device=None, map_shape=None):
+                  special_weight=None, healpix=False, device=None, map_shape=None, ground=False):
     """Destriper.run_destriper (Destriper.py:456-503) on the GPU.
 
     ``pixel_edges[-1] + 1`` is the map size (bin_offset_map, :169).  Returns
     {'All': maps} with host NumPy maps on rank 0; other ranks get None maps.
     map_shape (ny, nx), an extension: the map's row-major layout, which lets the
-    operator run on a 2-D tiled pixel order (DeviceDestriper)."""
+    operator run on a 2-D tiled pixel order (DeviceDestriper).
+    ground=True, an extension: fit an azimuth slope and a level per (observation, feed)
+    from ``az``, ``feedid`` and ``obsids`` jointly with the offsets (the reference's
+    op_Ax_with_ground, :265-336, which its run() leaves switched off); the result gains
+    'Ground': {'obsids', 'feeds', 'slope', 'level'} (one rank only)."""
     if special_weight is not None:
         raise NotImplementedError('special_weight is unused by run_destriper in the reference (:482)')
     import torch
     if device is None:
         device = torch.cuda.current_device()
     npix = int(pixel_edges[-1]) + 1
+    if ground:
+        if az is None or feedid is None or obsids is None:
+            raise ValueError('ground=True needs az, feedid and obsids')
+        dd = DeviceDestriper(np.asarray(_pointing), np.asarray(_tod, dtype=np.float64),
+                             np.asarray(_weights, dtype=np.float64), int(offset_length), npix, device,
+                             map_shape=map_shape, ground=(np.asarray(az, dtype=np.float64), feedid, obsids))
+        res = dd.solve(threshold, niter, to_host=True)
+        return {'All': res['maps'], 'Ground': res['ground']}
     dd = DeviceDestriper(np.asarray(_pointing), np.asarray(_tod, dtype=np.float64),
                          np.asarray(_weights, dtype=np.float64), int(offset_length), npix, device, map_shape=map_shape)
     res = dd.solve(threshold, niter, to_host=True)

@@ -125,14 +125,19 @@ def main(filelistname, offset_length=50, feed_weights=None, prefix='fg9', output
          feeds=[1, 2, 3, 5, 6, 9, 11, 12, 13, 14, 15, 16, 17, 18, 19], nxpix=480, nypix=480,
          crval=['05:32:00.3', '+12:30:28.0'], crpix=[240, 240], ctype=['RA---CAR', 'DEC--CAR'],
          cdelt=[-0.016666, 0.016666], use_gain_filter=True, calibration=True, calibrator='TauA', threshold=1e-6,
-         niter=100, healpix=False, bands=(0, 1, 2, 3), store=None, device=None, batch_bands=True):
+         niter=100, healpix=False, bands=(0, 1, 2, 3), store=None, device=None, batch_bands=True, ground=False):
     """run_destriper.main (run_destriper.py:79-189).  ``store`` (tests) maps
     filename -> (datasets, attrs) instead of reading files; ``device`` is the
     rank's GPU (default: torch's current device, LOCAL_RANK under torchrun).
     ``batch_bands``: the bands share the pointing, so they are read with one
     batched median call and solved as ONE batched device system
     (read_comap_data_bands + run_destriper_bands); False runs the reference's
-    per-band loop.  The maps are the same either way."""
+    per-band loop.  The maps are the same either way.
+    ``ground`` ([Inputs] ground_template in the .ini, absent = False): also fit an azimuth
+    slope and a level per (observation, feed) jointly with the offsets (the reference's
+    op_Ax_with_ground, Destriper.py:265-336, which its run() leaves switched off).  This
+    takes the per-band loop, which reads az / feedid / obsids; rank 0 writes each band's fit
+    to <output_dir>/<prefix>_ground_band<iband>.npz and the band's entry gains 'Ground'."""
     rank, size = _rank_size()
     if device is None:
         import torch
@@ -156,7 +161,7 @@ def main(filelistname, offset_length=50, feed_weights=None, prefix='fg9', output
         offset_length = 250
         threshold = 1
     out = {}
-    if batch_bands and len(bands) > 1:
+    if batch_bands and len(bands) > 1 and not ground:
         r = COMAPData.read_comap_data_bands(filelist, map_info, bands=bands, offset_length=offset_length, feeds=feeds,
                                             use_gain_filter=use_gain_filter, calibration=calibration,
                                             calibrator=calibrator, healpix=healpix, store=store, device=device)
@@ -181,12 +186,16 @@ def main(filelistname, offset_length=50, feed_weights=None, prefix='fg9', output
         pixel_edges = _healpix_edges(pointing) if healpix else np.arange(nxpix * nypix)
         maps = run_destriper(pointing, tod, weights, offset_length, pixel_edges, az, el, ra, dec, feedid, obsids,
                              obsid_cuts, threshold=threshold, niter=niter, chi2_cutoff=20,
-                             device=device, map_shape=None if healpix else (nypix, nxpix))
+                             device=device, map_shape=None if healpix else (nypix, nxpix), ground=ground)
+        sky = {'All': maps['All']}               # (the writers iterate the dict: the maps only)
         if rank == 0:
             if healpix:
-                write_map_healpix(prefix, maps, remap, map_info, output_dir, iband)
+                write_map_healpix(prefix, sky, remap, map_info, output_dir, iband)
             else:
-                write_map(prefix, maps, map_info, output_dir, iband)
+                write_map(prefix, sky, map_info, output_dir, iband)
+            if ground:
+                os.makedirs(output_dir, exist_ok=True)
+                np.savez(os.path.join(output_dir, '{}_ground_band{}.npz'.format(prefix, iband)), **maps['Ground'])
         out[iband] = maps
     return out
 
@@ -205,4 +214,5 @@ def cli(argv):
                 crpix=as_list(params['crpix']), ctype=as_list(params['ctype']), cdelt=as_list(params['cdelt']),
                 use_gain_filter=p['ReadData']['use_gain_filter'], calibration=p['ReadData']['calibration'],
                 calibrator=p['ReadData']['calibrator'], threshold=10 ** float(params['threshold']),
-                niter=int(params['niter']), healpix=params['healpix'])
+                niter=int(params['niter']), healpix=params['healpix'],
+                ground=bool(params.get('ground_template', False)))

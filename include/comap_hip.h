@@ -14,6 +14,7 @@
  *                            + Analysis/GainSubtraction.py:17-209
  *   comap_l1_channel_bin     Analysis/Level1Averaging.py:249-321 (Level1Averaging)
  *   comap_destripe_*         MapMaking/Destriper.py:85-263,402-503
+ *   comap_destripe_ground_*  MapMaking/Destriper.py:265-336 (op_Ax_with_ground)
  *   comap_prep_*             MapMaking/COMAPData.py:72-117,205-236,247-427,471-577
  *                            (read_comap_data / get_tod / read_pixels)
  *
@@ -350,6 +351,66 @@ int comap_offset_centroid_keys(comap_ctx *ctx, const int32_t *pix_dev, int64_t n
                                int64_t ny, const int32_t *lut_dev, int64_t n_internal, int32_t *key_dev);
 int comap_relabel_pixels(comap_ctx *ctx, const int32_t *pix_dev, int64_t n, const int32_t *lut_dev, int64_t npix,
                          int64_t n_internal, int32_t *out_dev);
+
+/* ------------------------------------------------------------ destriper ground template */
+/* The reference's op_Ax_with_ground (MapMaking/Destriper.py:265-336) on a one-band problem:
+ * an azimuth slope s_k and a level c_k per group k = (observation, feed), fitted jointly with
+ * the offsets.  Unknowns [x (N/L, internal offset order) | s (K) | c (K)]; sample t of offset o
+ * and group k is modelled as x_o + s_k a_t + c_k and A = [F G]^T W Z [F G] keeps the destriper's
+ * binning, its m_p = num_p where h_p == 0 and its m[pointing] wrap for negative pixel ids.
+ * Two deviations from the reference:
+ *   1. a_t = (az_t - mu_k) / sigma_k, with the plain mean and rms of the group's azimuths
+ *      (a_t = 0 where the group's azimuth is constant), not raw degrees: the same model space
+ *      (the level absorbs the shift), but a spectrum CG converges on.  In the reference's units
+ *      slope = s / sigma and level = c - s mu / sigma (the level only up to the offsets' null
+ *      space: a constant moved between c_k and the group's offsets changes no residual).
+ *   2. every offset belongs to one group: gid_dev int32 [N/L] in the caller's offset order,
+ *      values in [0, n_groups) (else -3).  The reference selects samples.
+ * The calls below add the ground terms around the plain problem's own calls, on the level-folded
+ * offsets x'_o = x_o + c_{g(o)} (comap_destripe_ground_fold):
+ *   num = comap_destripe_bin(x', mode 0);   comap_destripe_ground_bin(s, num)
+ *   y   = comap_destripe_project(x', num);  comap_destripe_ground_project(x', s, num, h, y, z)
+ * pixels / az / tod / weights [N] are the problem's samples (device).  n_bands must be 1.
+ * Built like the problem's set-up: a stable radix sort of the samples by (group, read pixel)
+ * and segment sums in sample order (deterministic); synchronises. */
+typedef struct comap_ground comap_ground;
+int comap_destripe_ground_create(comap_destriper *d, const int32_t *pixels_dev, const double *az_dev,
+                                 const double *tod_dev, const double *weights_dev, const int32_t *gid_dev,
+                                 int64_t n_groups, comap_ground **out);
+/* (destroy it before the problem it was created on) */
+int comap_destripe_ground_destroy(comap_ground *g);
+int64_t comap_destripe_ground_n_groups(const comap_ground *g);
+/* (group, pixel) entries: group-major (incl. off-map reads) and pixel-major (binned only) */
+int comap_destripe_ground_nnz(const comap_ground *g, int64_t *nnz_group_major, int64_t *nnz_pixel_major);
+/* mu_dev / sigma_dev f64 [K] (either may be NULL): each group's azimuth mean and rms */
+int comap_destripe_ground_stats(comap_ground *g, double *mu_dev, double *sigma_dev);
+/* xprime[i] = x[i] + c[g(i)] over the N/L offsets (internal order) */
+int comap_destripe_ground_fold(comap_ground *g, const double *x_dev, const double *c_dev, double *xprime_dev);
+/* num_p += sum over pixel row p of ga_e s_{k(e)}, ga_e = sum w a over group k's samples binned
+ * in p (a gather per pixel row; rows without entries are not touched) */
+int comap_destripe_ground_bin(comap_ground *g, const double *s_dev, double *num_dev);
+/* y_o += wa_o s_{g(o)} (y_dev in/out [N/L]: comap_destripe_project's output for x');
+ * z_dev [2K]: z[k] = sum_{o in k} wa_o x'_o + Saa_k s_k - sum over group row k of ga_e m[read
+ * pixel of e] (the slope rows), z[K + k] = sum_{o in k} y_o (the level rows); m = num / h on the
+ * fly (num where h == 0), h_dev == NULL: the local weight map.  Group rows are summed in fixed
+ * chunks, one workgroup each, and the partials in chunk order: no atomics, no host sync. */
+int comap_destripe_ground_project(comap_ground *g, const double *xprime_dev, const double *s_dev,
+                                  const double *num_dev, const double *h_dev, double *y_dev, double *z_dev);
+/* The right-hand side's tail from b_dev = comap_destripe_project(NULL, naive numerator):
+ * z[k] = Ta_k - sum over group row k of ga_e m_naive[read pixel of e], z[K + k] = sum_{o in k} b_o */
+int comap_destripe_ground_rhs(comap_ground *g, const double *num_dev, const double *h_dev, const double *b_dev,
+                              double *z_dev);
+/* The CG's vector algebra on the 2K-value tails (s | c) of its vectors, after the plain
+ * problem's call on their first N/L values (comap_destripe_dot / _cg_update / _cg_direction);
+ * every pointer is a tail [2K] or a device scalar; one workgroup, fixed-order sums:
+ *   tail_dot        dot += a . b
+ *   tail_update     alpha = rr/pq; x += alpha p; r -= alpha q; rr_new += r . r
+ *   tail_direction  p = r + (rr_new/rr) p */
+int comap_destripe_ground_tail_dot(comap_ground *g, const double *a_dev, const double *b_dev, double *dot_dev);
+int comap_destripe_ground_tail_update(comap_ground *g, const double *rr_dev, const double *pq_dev, double *x_dev,
+                                      double *r_dev, const double *p_dev, const double *q_dev, double *rr_new_dev);
+int comap_destripe_ground_tail_direction(comap_ground *g, const double *rr_new_dev, const double *rr_dev,
+                                         double *p_dev, const double *r_dev);
 
 /* ------------------------------------------------------------ destriper data prep (COMAPData.py) */
 /* One Level-2 file's inputs to comap_prep_gather (device pointers).  Output row r
