@@ -238,12 +238,19 @@ struct comap_l1_plan {
     double *mb = nullptr;              // [F][4][T] band mean
     double *mf = nullptr;              // [F][4][T] median-filtered band mean
     double *ssum = nullptr;            // [U*4][4]: Smf, Smm, SAm
-    double *sdm = nullptr;             // [U*4096] sum_t d mf
+    double *sdm = nullptr;             // [U*4096] sum_t d mf (pass C: pairs with needc only)
+    // regression without pass C: pass B's per-band gain sum, the dots of mf
+    // with pass B's three band sums, and the per-pair gate that sends a pair to pass C
+    double *sgb = nullptr;             // [F][4][T] per-band gain-template sum Sg_bt (pass B)
+    double *pdot = nullptr;            // [U*4][4]: P_g, P_r, P_o = sum_t mf_t S_K,bt (k_series_sums)
+    double *pgate = nullptr;           // [U*4][2]: listed row non-finite, coefficient magnitude bound (phase 0)
+    int32_t *needc = nullptr;          // [U*4] pair takes pass C and the per-channel solve
+    bool regress_legacy = false;       // COMAP_L1_REGRESS=legacy: needc everywhere
     double *gw = nullptr;              // [F][4096] gain weights w
     int32_t *gmode = nullptr;          // [F]
     double *kap = nullptr;             // [3][U*4096] kappa_g, kappa_r, kappa_o
     double *dsum = nullptr;            // [U*4][16] per-band constants for pass D
-    double *xreg = nullptr;            // [U*4096][2] regression x0,x1 (debug)
+    double *xreg = nullptr;            // [U*4096][2] regression x0,x1 (pairs with needc; else 0)
     double *dG = nullptr;              // [F][T]
     // NaN / calibrator paths
     int32_t *rowbad = nullptr;         // [U*4096] non-finite samples per row (pass A)

@@ -3,7 +3,7 @@
 // The reference reduces each (feed, scan) with NumPy/SciPy
 // (comancpipeline/Analysis/Level1Averaging.py:792-872).  Here every step is a
 // weighted sum of the raw f32 cube d[f][b][c][t] with per-channel f64
-// coefficients, so the whole observation is three streaming passes over HBM:
+// coefficients, so the whole observation is two streaming passes over HBM:
 //
 //   pass A  k_moments      per channel, over t: sum d, sum A d, and the
 //                          stride-4 difference moments (atmosphere fit +
@@ -13,9 +13,14 @@
 //                          every per-sample output sum (gain template, residual
 //                          and original band sums)              -> 4 B/samp·ch
 //           median_kernels.hip: the w = 6000 running median of the band means
-//   pass C  k_regress      per channel, over t: sum d mf        -> 4 B/samp·ch
+//           k_series_sums: the series sums of the regression and the dots of the
+//                          filtered band mean with pass B's per-band sums
 //
-// The regression enters the outputs only through per-band constants (k_finish);
+// The regression enters the outputs only through per-band constants (k_finish),
+// and those are linear in sum_t d mf, so they follow from the dots above: the
+// former pass C (k_regress, per channel over t: sum d mf) and the per-channel
+// solve run only for the (unit, band) pairs a device-side gate sends there
+// (needc: non-finite data or sums, a singular system, COMAP_L1_REGRESS=legacy).
 // k_gain_avg (the former pass D) runs only when a NaN regression coefficient
 // changes a channel weight (k_coef_d phase 1 flags it).
 //
@@ -28,6 +33,7 @@
 #include "comap_internal.h"
 
 #include <algorithm>
+#include <cfloat>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -545,12 +551,13 @@ __global__ void __launch_bounds__(256) k_coef_b(const int32_t *__restrict__ unit
 // One read of the cube BEFORE the median serves every per-sample channel sum
 // of the reduction (Level1Averaging.py:691-692, 841-867; GainSubtraction.py:201):
 //   m_t   = (sum_c alpha_c d_ct - beta - gamma A_t) / N      band mean -> median
-//   Sg_t  = sum_b sum_c kg_c d_ct                             gain template (dG)
+//   Sg_t  = sum_b Sg_bt,  Sg_bt = sum_c kg_c d_ct             gain template (dG)
 //   Sr_bt = sum_c kr_c d_ct,  So_bt = sum_c ko_c d_ct         residual / original band sums
 // The kappa weights (k_coef_d phase 0) depend on the regression only through
 // a NaN coefficient, which phase 1 detects (then the legacy pass D runs), so
 // they are known here; the regression enters later only through per-band
-// constants (k_finish).  The wave walks its (unit, band)'s channel list
+// constants (k_finish).  Sg_bt, Sr_bt and So_bt are also kept per band: their
+// dots with mf replace pass C (k_series_sums).  The wave walks its (unit, band)'s channel list
 // (k_coef_d phase 0: the median channels with alpha != 0, a superset of the
 // kappa channels) four entries at a time, 4 x kJB 16-B loads in flight.
 
@@ -645,7 +652,7 @@ __global__ void __launch_bounds__(256) k_band_sums(const float *__restrict__ tod
                                                    const int32_t *__restrict__ dcnt, const double *__restrict__ dw,
                                                    const double *__restrict__ bsum, double *__restrict__ mb,
                                                    double *__restrict__ sr_out, double *__restrict__ so_out,
-                                                   double *__restrict__ sg_out)
+                                                   double *__restrict__ sg_out, double *__restrict__ sgb_out)
 {
     __shared__ double sg[kBands][256 * kJB];
     const int b = uniform(threadIdx.x >> 6);
@@ -683,6 +690,7 @@ __global__ void __launch_bounds__(256) k_band_sums(const float *__restrict__ tod
             mb[rowo + o] = cn > 0 ? (acc.m[i] - beta - gamma * a[o]) / cn : NAN;
             sr_out[rowo + o] = acc.r[i];
             so_out[rowo + o] = acc.o[i];
+            sgb_out[rowo + o] = acc.g[i];           // per band: k_series_sums dots it with mf
             if (b == 0) {
                 const int tl = 256 * g + 4 * lane + e;
                 sg_out[(int64_t)f * T + t0 + r0 + o] = (sg[0][tl] + sg[1][tl]) + (sg[2][tl] + sg[3][tl]);
@@ -690,33 +698,75 @@ __global__ void __launch_bounds__(256) k_band_sums(const float *__restrict__ tod
         }
 }
 
-// ------------------------------------------------------------------ series sums for pass C
+// ------------------------------------------------------------------ series sums and dots (the regression)
 // ss[ub] = {sum mf, sum mf^2, sum A mf}; zeroes mf of skipped bands.
+//
+// The regression without pass C.  The per-channel solution (x0_c, x1_c) reaches the
+// outputs only through sum_c k_c x_c for the three weightings k (k_coef_d), and x is
+// linear in sdm_c = sum_t d_ct mf_t, so all that is needed of pass C is
+//   sum_c kappa_c sdm_c = sum_t mf_t (sum_c kappa_c d_ct) = sum_t mf_t S_K,bt = P_K
+// with S_K,bt the band sums pass B left in sgb / tod_out / orig_out (read here before
+// k_finish overwrites them): pd[ub] = {P_g, P_r, P_o}, summed in a fixed order.
+//
+// needc[ub] = 1 sends the pair through pass C and the per-channel solve instead.  It
+// stays 0 only when every listed channel's x is certainly finite, so that no kappa can
+// depend on it: the series sums, det and the dots are finite, det != 0,
+// no listed row holds a non-finite sample or sum (pg[0], phase 0), and a bound on every
+// product of the solve, from the coefficient magnitudes pg[1] and |d| <= FLT_MAX, stays
+// far inside the f64 range.  force: every pair (COMAP_L1_REGRESS=legacy, special rows).
+constexpr double kGateMax = 1e300;
 __global__ void __launch_bounds__(256) k_series_sums(int ub0, const int32_t *__restrict__ units, const double *__restrict__ A,
                                                      int64_t T, const double *__restrict__ bsum,
-                                                     double *__restrict__ mf, double *__restrict__ ss)
+                                                     double *__restrict__ mf, double *__restrict__ ss,
+                                                     const double *__restrict__ sgb, const double *__restrict__ sr,
+                                                     const double *__restrict__ so, const double *__restrict__ pg,
+                                                     int force, double *__restrict__ pd, int32_t *__restrict__ needc)
 {
     __shared__ double red[4];
     const int ub = ub0 + blockIdx.x;
     const int u = ub / kBands, b = ub % kBands;
     const int f = units[4 * u], t0 = units[4 * u + 2], n = units[4 * u + 3];
     const bool run = bsum[4 * (int64_t)ub + 3] > 0;
-    double *m = mf + (int64_t)(f * kBands + b) * T + t0;
+    const int64_t row = (int64_t)(f * kBands + b) * T + t0;
+    double *m = mf + row;
     const double *a = A + (int64_t)f * T + t0;
-    double s0 = 0, s1 = 0, s2 = 0;
+    const double *xg = sgb + row, *xr = sr + row, *xo = so + row;
+    double s0 = 0, s1 = 0, s2 = 0, p0 = 0, p1 = 0, p2 = 0;
     for (int t = threadIdx.x; t < n; t += blockDim.x) {
         if (!run) { m[t] = 0.0; continue; }
         const double x = m[t];
         s0 += x;
         s1 = fma(x, x, s1);
         s2 = fma(a[t], x, s2);
+        p0 = fma(x, xg[t], p0);
+        p1 = fma(x, xr[t], p1);
+        p2 = fma(x, xo[t], p2);
     }
     s0 = block_sum256(s0, red);
     s1 = block_sum256(s1, red);
     s2 = block_sum256(s2, red);
+    p0 = block_sum256(p0, red);
+    p1 = block_sum256(p1, red);
+    p2 = block_sum256(p2, red);
     if (threadIdx.x == 0) {
         double *o = ss + 4 * (int64_t)ub;
         o[0] = s0; o[1] = s1; o[2] = s2;
+        double *q = pd + 4 * (int64_t)ub;
+        q[0] = p0; q[1] = p1; q[2] = p2;
+        int32_t need = force ? 1 : 0;
+        if (run && !force) {      // a skipped band has no regression at all
+            const double nn = (double)n, det = nn * s1 - s0 * s0;
+            const double *g = pg + 2 * (int64_t)ub;
+            // |sym_c| <= B (D + 2 S); every numerator of the solve <= 2 S B (D + 2 S)
+            const double S = fmax(fmax(nn, fabs(s0)), fmax(s1, fabs(s2)));
+            const double D = nn * (double)FLT_MAX * sqrt(s1);
+            const double bound = 2.0 * S * g[1] * (D + 2.0 * S);
+            const bool ok = isfinite(s0) && isfinite(s1) && isfinite(s2) && isfinite(det) && det != 0.0 &&
+                            g[0] == 0.0 && isfinite(p0) && isfinite(p1) && isfinite(p2) &&
+                            bound < kGateMax && bound / fabs(det) < kGateMax;
+            need = ok ? 0 : 1;
+        }
+        needc[ub] = need;
     }
 }
 
@@ -733,7 +783,8 @@ constexpr int kRegBlocks = kChannels / (4 * kRPW);   // blocks per (unit, band)
 __global__ void __launch_bounds__(256) k_regress(int ub0, const float *__restrict__ tod, const double *__restrict__ mf,
                                                  const int32_t *__restrict__ units, int64_t T,
                                                  const double *__restrict__ bsum, const int32_t *__restrict__ dlist,
-                                                 const int32_t *__restrict__ dcnt, double *__restrict__ sdm)
+                                                 const int32_t *__restrict__ dcnt, const int32_t *__restrict__ needc,
+                                                 double *__restrict__ sdm)
 {
     const int wid = uniform(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
@@ -742,6 +793,7 @@ __global__ void __launch_bounds__(256) k_regress(int ub0, const float *__restric
     const int cnt = dcnt[ub];
     const int j0 = g * 4 * kRPW + wid * kRPW;
     if (bsum[4 * (int64_t)ub + 3] <= 0) return;      // band skipped by median_filter (block-uniform)
+    if (needc[ub] == 0) return;                      // regression formed from pass B's sums (k_series_sums)
     if (j0 >= cnt) return;
     const int f = units[4 * u], t0 = units[4 * u + 2], n = units[4 * u + 3];
     const int32_t *lst = dlist + (int64_t)ub * kChannels;
@@ -978,7 +1030,8 @@ __global__ void __launch_bounds__(256) k_coef_d(const int32_t *__restrict__ unit
                                                 const int32_t *__restrict__ rowbad, const float *__restrict__ tod,
                                                 int64_t T, const double *__restrict__ A,
                                                 const double *__restrict__ mf, const int32_t *__restrict__ ynf,
-                                                const int32_t *__restrict__ ugate)
+                                                const int32_t *__restrict__ ugate, const double *__restrict__ pd,
+                                                double *__restrict__ pg, const int32_t *__restrict__ needc)
 {
     __shared__ double red[4];
     __shared__ double s_kap[4][kChannels];     // alpha, kg, kr, ko (phase 0 channel list)
@@ -1007,6 +1060,12 @@ __global__ void __launch_bounds__(256) k_coef_d(const int32_t *__restrict__ unit
     const bool zero = gain_called;
     const bool use_dg = gain_called && gm == 0 && !ynf[u];
     const double det = n * Smm - Smf * Smf;
+    // fused: the pair's band constants come from pass B's sums (k_series_sums: pd, needc);
+    // the loop then runs as in phase 0 (x = 0: under the gate no kappa depends on x) and
+    // sums kappa o, kappa a and kappa (Sd - n o - a SA) per weighting instead of k f
+    const bool fused = phase != 0 && band_on && needc[ub] == 0;      // block-uniform
+    const bool solve = phase != 0 && !fused;
+    double pbad = 0.0, pmag = 0.0;      // phase 0: the gate's inputs over the listed channels
     double acc[12];
 #pragma unroll
     for (int k = 0; k < 12; ++k) acc[k] = 0.0;
@@ -1022,10 +1081,14 @@ __global__ void __launch_bounds__(256) k_coef_d(const int32_t *__restrict__ unit
         double fa = 0, fb = 0, fg = 0, fd = 0, x0 = 0, x1 = 0;
         if (band_on && median_channel(c)) {
             if (al != 0.0) {
-                const double sdmi = (phase != 0) ? sdm[i] : 0.0;   // pass C (every listed channel)
+                const double sdmi = solve ? sdm[i] : 0.0;   // pass C (every listed channel of a needc pair)
                 const double sy = al * (mom[i] - n * o - a * SA);
                 const double sym = al * (sdmi - o * Smf - a * SAm);
-                if (phase != 0) {    // phase 0: x unknown yet; kappa never depends on x unless x is NaN
+                if (phase == 0) {
+                    if (rowbad[i] > 0 || !isfinite(mom[i]) || !isfinite(sy)) pbad = 1.0;
+                    pmag += fabs(al) * (fabs(o) + fabs(a) + 1.0) + fabs(sy);
+                }
+                if (solve) {         // phase 0: x unknown yet; kappa never depends on x unless x is NaN
                     if (isfinite(sy) && isfinite(sym)) {
                         x0 = (Smm * sy - Smf * sym) / det;
                         x1 = (n * sym - Smf * sy) / det;
@@ -1057,7 +1120,7 @@ __global__ void __launch_bounds__(256) k_coef_d(const int32_t *__restrict__ unit
         if (special) {          // out of the fused sums; its weights from y at the scan's first sample
             kr = ko = 0.0;
             W = Wo = 0.0;
-            if (phase != 0) {
+            if (solve) {
                 const int t0 = units[4 * u + 2];
                 const float d0 = tod[((int64_t)f * kBC + b * kChannels + c) * T + t0];
                 const double y0 = special_y(al, o, a, x0, x1, d0, A[(int64_t)f * T + t0],
@@ -1069,7 +1132,7 @@ __global__ void __launch_bounds__(256) k_coef_d(const int32_t *__restrict__ unit
         const double kgfa = (kg == 0.0) ? 0.0 : kg * fa;
         const double krfa = (kr == 0.0) ? 0.0 : kr * fa;
         const double kofa = (ko == 0.0) ? 0.0 : ko * fa;
-        if (phase >= 1) {        // kappa with the regression (and the gate) known must equal the earlier kappa
+        if (solve) {             // kappa with the regression (and the gate) known must equal the earlier kappa
             if (__double_as_longlong(kap[i]) != __double_as_longlong(kgfa) ||
                 __double_as_longlong(kap[UC + i]) != __double_as_longlong(krfa) ||
                 __double_as_longlong(kap[2 * UC + i]) != __double_as_longlong(kofa))
@@ -1082,18 +1145,48 @@ __global__ void __launch_bounds__(256) k_coef_d(const int32_t *__restrict__ unit
         s_kap[1][c] = kgfa;
         s_kap[2][c] = krfa;
         s_kap[3][c] = kofa;
-        if (kg != 0.0) { acc[0] += kg * fb; acc[1] += kg * fg; acc[2] += kg * fd; }
-        if (kr != 0.0) { acc[3] += kr * fb; acc[4] += kr * fg; acc[5] += kr * fd; acc[9] += kr; }
-        if (ko != 0.0) { acc[6] += ko * fb; acc[7] += ko * fg; acc[8] += ko * fd; }
+        if (fused) {             // kappa exactly as phase 0 formed it (and pass B applied it)
+            const double sd = mom[i] - n * o - a * SA;
+            if (kgfa != 0.0) { acc[0] += kgfa * o; acc[1] += kgfa * a; acc[2] += kgfa * sd; }
+            if (krfa != 0.0) { acc[3] += krfa * o; acc[4] += krfa * a; acc[5] += krfa * sd; }
+            if (kofa != 0.0) { acc[6] += kofa * o; acc[7] += kofa * a; acc[8] += kofa * sd; }
+            if (kr != 0.0) acc[9] += kr;
+        } else {
+            if (kg != 0.0) { acc[0] += kg * fb; acc[1] += kg * fg; acc[2] += kg * fd; }
+            if (kr != 0.0) { acc[3] += kr * fb; acc[4] += kr * fg; acc[5] += kr * fd; acc[9] += kr; }
+            if (ko != 0.0) { acc[6] += ko * fb; acc[7] += ko * fg; acc[8] += ko * fd; }
+        }
         acc[10] += W;
         acc[11] += Wo;
     }
 #pragma unroll
     for (int k = 0; k < 12; ++k) acc[k] = block_sum256(acc[k], red);
     if (threadIdx.x == 0 && phase != 0) {
+        if (fused) {
+            // sum_c k_c x_c from the sums: sum k sym = P_K - Smf sum(kappa o) - SAm sum(kappa a)
+            const double *P = pd + 4 * (int64_t)ub;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const double sko = acc[3 * j], ska = acc[3 * j + 1], ksy = acc[3 * j + 2];
+                const double ksym = P[j] - Smf * sko - SAm * ska;
+                const double kx0 = (Smm * ksy - Smf * ksym) / det;
+                const double kx1 = (n * ksym - Smf * ksy) / det;
+                acc[3 * j] = -(sko + kx0);
+                acc[3 * j + 1] = -ska;
+                acc[3 * j + 2] = -kx1;
+            }
+        }
         double *o = dsum + 16 * (int64_t)ub;
 #pragma unroll
         for (int k = 0; k < 12; ++k) o[k] = acc[k];
+    }
+    if (phase == 0) {
+        pbad = block_sum256(pbad, red);
+        pmag = block_sum256(pmag, red);
+        if (threadIdx.x == 0) {
+            pg[2 * (int64_t)ub] = pbad;
+            pg[2 * (int64_t)ub + 1] = pmag + 1.0;
+        }
     }
     __syncthreads();
     if (phase == 0 && threadIdx.x < 64) {
@@ -1656,6 +1749,10 @@ extern "C" int comap_l1_plan_create(comap_ctx *ctx, const comap_obs_desc *d, com
     rc |= dalloc(ctx, &p->mf, (size_t)p->F * kBands * p->T);
     rc |= dalloc(ctx, &p->ssum, 4 * (size_t)p->U * kBands);
     rc |= dalloc(ctx, &p->sdm, UC);
+    rc |= dalloc(ctx, &p->sgb, (size_t)p->F * kBands * p->T);
+    rc |= dalloc(ctx, &p->pdot, 4 * (size_t)p->U * kBands);
+    rc |= dalloc(ctx, &p->pgate, 2 * (size_t)p->U * kBands);
+    rc |= dalloc(ctx, &p->needc, (size_t)p->U * kBands);
     rc |= dalloc(ctx, &p->gw, (size_t)p->F * kBC);
     rc |= dalloc(ctx, &p->gmode, p->F);
     rc |= dalloc(ctx, &p->kap, 3 * (size_t)UC);
@@ -1669,6 +1766,12 @@ extern "C" int comap_l1_plan_create(comap_ctx *ctx, const comap_obs_desc *d, com
     rc |= dalloc(ctx, &p->ynf, (size_t)p->U);
     rc |= dalloc(ctx, &p->ugate, (size_t)p->U);
     if (rc) { delete p; return -2; }
+    // COMAP_L1_REGRESS=fused (default) | legacy: legacy sends every (unit, band) through
+    // pass C and the per-channel solve (needc everywhere) -- the comparison path
+    if (const char *r = getenv("COMAP_L1_REGRESS")) {
+        if (!strcmp(r, "legacy")) p->regress_legacy = true;
+        else if (strcmp(r, "fused")) { comap_l1_plan_destroy(p); return comap_fail(ctx, -1, "COMAP_L1_REGRESS must be fused or legacy"); }
+    }
     // pass B / median / pass C pipeline groups (comap_l1_average): contiguous unit ranges
     // COMAP_GROUPS (env) overrides the compiled default -- measurement knob
     int groups = COMAP_GROUPS;
@@ -1737,7 +1840,8 @@ extern "C" int comap_l1_plan_destroy(comap_l1_plan *p)
                     p->nan_count, p->alpha, p->nf, p->bsum, p->mb, p->mf, p->ssum, p->sdm, p->gw,
                     p->gmode, p->kap, p->dsum, p->xreg, p->dG, p->rowbad, p->ubs, p->fitsum, p->oa,
                     p->flag, p->dlist, p->dcnt, p->dw, p->nanpos, p->nanpos_n, p->vane_dev,
-                    p->sel_pairs, p->sel_voff, p->sel_flag, p->sel_valid, p->ynf, p->ugate};
+                    p->sel_pairs, p->sel_voff, p->sel_flag, p->sel_valid, p->ynf, p->ugate, p->sgb, p->pdot,
+                    p->pgate, p->needc};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     for (int g = 0; g < comap_l1_plan::kMaxGroups; ++g) {
@@ -2011,11 +2115,13 @@ extern "C" int comap_l1_average(comap_l1_plan *p, const double *fit, const doubl
     COMAP_LAUNCH_CHECK(ctx);
     // +-inf samples left after the NaN fill (pass A counted them): special rows (k_special_rows)
     const bool special = p->nan_total > 0;
+    // the special-row path needs every channel's x (xreg): all pairs take pass C, as does legacy mode
+    const int force_c = (special || p->regress_legacy) ? 1 : 0;
     auto coef_d = [&](int phase, const int32_t *ugate) {
         k_coef_d<<<UB, 256, 0, st>>>(p->units, p->unit_sums, p->mom, UC, p->oa, p->alpha, p->nf, p->bsum, p->ssum,
                                      p->sdm, tsys0, gain0, p->gw, p->gmode, calibrator, p->kap, p->dsum, p->xreg,
                                      phase, p->flag, p->dlist, p->dcnt, p->dw, p->rowbad, p->tod, p->T, p->airmass,
-                                     p->mf, p->ynf, ugate);
+                                     p->mf, p->ynf, ugate, p->pdot, p->pgate, p->needc);
     };
     auto special_rows = [&](int mode) {
         k_special_rows<<<UB, 256, 0, st>>>(mode, p->units, p->tod, p->T, p->airmass, p->mf, p->oa, p->alpha, p->nf,
@@ -2025,10 +2131,12 @@ extern "C" int comap_l1_average(comap_l1_plan *p, const double *fit, const doubl
     // phase 0: the kappa weights and the channel list (no regression needed)
     PROF(p, KV_COEF_D, coef_d(0, nullptr));
     COMAP_LAUNCH_CHECK(ctx);
-    // Pass B (band means + every per-sample output sum), the sliding median and pass C
-    // (regression sums) are software-pipelined over the unit groups on two streams:
+    // Pass B (band means + every per-sample output sum), the sliding median with the series
+    // sums and dots that stand in for pass C, and pass C itself (regression sums, only for
+    // the pairs k_series_sums gated out: needc) are software-pipelined over the unit groups:
     //   main: B0 B1 .. | wait M0: C0 | wait M1: C1 ..     side: wait B0: M0 | wait B1: M1 ..
-    // so each group's median (latency-bound) runs under the next group's streaming pass.
+    // so each group's median (latency-bound) runs under the next group's streaming pass;
+    // the main stream has waited for every group's median before phase 1.
     // one group: the median stays on the main stream -- the two cross-stream event hops
     // cost ~20 us each at the C3 shard (r03s2 trace) and there is nothing to overlap
     hipStream_t side = p->ngroups > 1 ? p->side : st;
@@ -2037,7 +2145,7 @@ extern "C" int comap_l1_average(comap_l1_plan *p, const double *fit, const doubl
         const int ub0 = p->grp_u0[g] * kBands, nub = (p->grp_u0[g + 1] - p->grp_u0[g]) * kBands;
             PROF(p, KV_BAND_SUMS, k_band_sums<<<kSubB * nt, 256, 0, st>>>(p->tod, p->airmass, p->units, p->tiles_b, t0,
                                                                         p->T, p->dlist, p->dcnt, p->dw, p->bsum,
-                                                                        p->mb, tod_out, orig_out, p->dG));
+                                                                        p->mb, tod_out, orig_out, p->dG, p->sgb));
         COMAP_LAUNCH_CHECK(ctx);
         if (side != st) {
             COMAP_CHECK(ctx, hipEventRecord(p->ev_b[g], st));
@@ -2046,7 +2154,9 @@ extern "C" int comap_l1_average(comap_l1_plan *p, const double *fit, const doubl
         PROF_ON(p, KV_MEDIAN, side, rc = comap_median_run(ctx, &p->medg[g], side));
         if (rc) return rc;
         PROF_ON(p, KV_SERIES_SUMS, side, k_series_sums<<<nub, 256, 0, side>>>(ub0, p->units, p->airmass, p->T,
-                                                                             p->bsum, p->mf, p->ssum));
+                                                                             p->bsum, p->mf, p->ssum, p->sgb, tod_out,
+                                                                             orig_out, p->pgate, force_c, p->pdot,
+                                                                             p->needc));
         COMAP_LAUNCH_CHECK(ctx);
         if (side != st) COMAP_CHECK(ctx, hipEventRecord(p->ev_m[g], side));
     }
@@ -2054,10 +2164,11 @@ extern "C" int comap_l1_average(comap_l1_plan *p, const double *fit, const doubl
         const int ub0 = p->grp_u0[g] * kBands, nub = (p->grp_u0[g + 1] - p->grp_u0[g]) * kBands;
         if (side != st) COMAP_CHECK(ctx, hipStreamWaitEvent(st, p->ev_m[g], 0));
         PROF(p, KV_REGRESS, k_regress<<<nub * kRegBlocks, 256, 0, st>>>(ub0, p->tod, p->mf, p->units, p->T, p->bsum,
-                                                                       p->dlist, p->dcnt, p->sdm));
+                                                                       p->dlist, p->dcnt, p->needc, p->sdm));
         COMAP_LAUNCH_CHECK(ctx);
     }
-    // phase 1: regression solve, per-band constants, kappa re-check
+    // phase 1: per-band constants -- from pass B's sums, or for needc pairs from the
+    // per-channel regression solve with the kappa re-check
     PROF(p, KV_COEF_D, coef_d(1, nullptr));
     COMAP_LAUNCH_CHECK(ctx);
     if (special) {
@@ -2168,12 +2279,21 @@ extern "C" int comap_l1_debug_fetch(comap_l1_plan *p, int32_t what, double *out,
     case 0: src = p->nf; cnt = UC; break;
     case 1: src = p->mf; cnt = (int64_t)p->F * kBands * p->T; break;
     case 2: src = p->dG; cnt = (int64_t)p->F * p->T; break;
-    case 3: src = p->xreg; cnt = 2 * UC; break;
+    case 3: src = p->xreg; cnt = 2 * UC; break;      // valid only for pairs with needc (case 10)
     case 4: src = p->mb; cnt = (int64_t)p->F * kBands * p->T; break;
     case 5: src = p->kap; cnt = 3 * UC; break;
     case 6: src = p->dsum; cnt = (int64_t)p->U * kBands * 16; break;
     case 7: src = p->alpha; cnt = UC; break;
     case 8: src = p->oa; cnt = 2 * UC; break;
+    case 10: {  // needc per (unit, band): 1 = pass C and the per-channel solve ran for the pair
+        const int UB = p->U * kBands;
+        if (n < (int64_t)UB) return comap_fail(ctx, -1, "debug buffer too small");
+        std::vector<int32_t> c(UB);
+        COMAP_CHECK(ctx, hipMemcpyAsync(c.data(), p->needc, 4 * (size_t)UB, hipMemcpyDeviceToHost, ctx->stream));
+        COMAP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+        for (int i = 0; i < UB; ++i) out[i] = c[i];
+        return 0;
+    }
     case 9: {   // per (unit, band): channel-list length, median band on
         const int UB = p->U * kBands;
         if (n < 2 * (int64_t)UB) return comap_fail(ctx, -1, "debug buffer too small");

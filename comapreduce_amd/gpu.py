@@ -325,10 +325,12 @@ class GPUObservation:
 
     KERNELS = ('vane', 'moments', 'atmos_fit', 'coef_b', 'band_sums', 'median', 'series_sums', 'regress',
                'gain_weights', 'coef_d', 'gain_avg', 'scan_weights', 'unused', 'finish')
-    # the HBM streaming passes: A (per-channel moments), B (band means + every per-sample
-    # output sum) and C (regression sums); gain_avg is the legacy pass D, launched but idle
-    # unless a NaN regression coefficient needs it
-    STREAMING = ('moments', 'band_sums', 'regress')
+    # the HBM streaming passes: A (per-channel moments) and B (band means + every per-sample
+    # output sum).  The regression's band constants come from pass B's sums (series_sums);
+    # regress (pass C) is launched but reads only the (unit, band) pairs the device-side
+    # gate sends it (debug(10): non-finite data, COMAP_L1_REGRESS=legacy), like gain_avg,
+    # the legacy pass D, idle unless a NaN regression coefficient needs it
+    STREAMING = ('moments', 'band_sums')
 
     def profile(self, enable=True):
         """Record HIP events around every kernel launch of this plan (True / 2), around
@@ -347,26 +349,29 @@ class GPUObservation:
 
     def pass_fractions(self) -> dict:
         """Fraction of the cube's (unit, band, channel) rows each streaming pass reads:
-        A all; B the channel list (median channels with finite alpha); C the list of the
-        bands the median filter did not skip.  Rows are weighted by scan length."""
+        A all; B the channel list (median channels with finite alpha); C ('regress') the
+        list of the pairs it actually read in the last reduction (needc, and the median
+        filter did not skip the band).  Rows are weighted by scan length."""
         d = self.debug(9).reshape(-1, 4, 2)
+        need = self.debug(10).reshape(-1, 4)
         n = self.units[:, 3].astype(np.float64)[:, None]
         tot = float(n.sum()) * 4 * N_CHANNELS
         return {'moments': 1.0, 'band_sums': float((d[..., 0] * n).sum()) / tot,
-                'regress': float((d[..., 0] * d[..., 1] * n).sum()) / tot}
+                'regress': float((d[..., 0] * d[..., 1] * need * n).sum()) / tot}
 
     def scan_samples(self) -> int:
         """Sum over units of the scan lengths (samples each streaming pass visits per channel)."""
         return int(self.units[:, 3].sum())
 
     def debug(self, what: int):
-        """Internal arrays (host f64): 0 rms [U,4,1024]; 1 mf [F,4,T]; 2 dG [F,T]; 3 x [U,4,1024,2]; 4 mb;
-        5 kappa [3,U,4,1024]; 6 pass-D sums [U,4,16]; 7 alpha [U,4,1024]; 8 atmosphere (o, a) [U,4,1024,2];
-        9 per (unit, band): channel-list length, median band on [U,4,2]."""
+        """Internal arrays (host f64): 0 rms [U,4,1024]; 1 mf [F,4,T]; 2 dG [F,T]; 3 x [U,4,1024,2] (valid
+        only for pairs with needc); 4 mb; 5 kappa [3,U,4,1024]; 6 pass-D sums [U,4,16]; 7 alpha [U,4,1024];
+        8 atmosphere (o, a) [U,4,1024,2]; 9 per (unit, band): channel-list length, median band on [U,4,2];
+        10 needc [U,4]: the pair took pass C and the per-channel regression solve."""
         U = self.units.shape[0]
         shapes = {0: (U, 4, 1024), 1: (self.F, 4, self.T), 2: (self.F, self.T), 3: (U, 4, 1024, 2),
                   4: (self.F, 4, self.T), 5: (3, U, 4, 1024), 6: (U, 4, 16), 7: (U, 4, 1024), 8: (U, 4, 1024, 2),
-                  9: (U, 4, 2)}
+                  9: (U, 4, 2), 10: (U, 4)}
         out = np.empty(shapes[what])
         self._bind()
         N.check(N.lib().comap_l1_debug_fetch(self.plan, what, N.hptr(out, ctypes.c_double), out.size), self.ctx,

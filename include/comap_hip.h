@@ -159,10 +159,13 @@ int comap_l1_channel_bin(comap_l1_plan *plan, int32_t bin_size, const double *we
 
 /* Debug/inspection: copies internal per-unit arrays (host f64):
  * what = 0: normalisation rms [U][4][1024]; 1: median-filtered band mean
- * [F][4][T]; 2: dG [F][T]; 3: regression x0,x1 [U][4][1024][2]; 4: band mean
+ * [F][4][T]; 2: dG [F][T]; 3: regression x0,x1 [U][4][1024][2] (valid only
+ * for the (unit, band) pairs that took pass C, code 10; 0 elsewhere); 4: band mean
  * [F][4][T]; 5: kappa [3][U][4][1024]; 6: per-band constants [U][4][16];
  * 7: alpha [U][4][1024]; 8: offsets/slopes [U][4][1024][2]; 9: per (unit,
- * band) channel-list length and median-band flag [U][4][2]. */
+ * band) channel-list length and median-band flag [U][4][2]; 10: needc [U][4],
+ * 1 where pass C and the per-channel regression solve ran for the pair
+ * (COMAP_L1_REGRESS=legacy, read at plan creation, sets it everywhere). */
 int comap_l1_debug_fetch(comap_l1_plan *plan, int32_t what, double *out_host, int64_t n);
 
 /* Per-kernel timing with HIP events recorded on the launching stream around
