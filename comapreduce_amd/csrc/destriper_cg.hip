@@ -6,40 +6,14 @@
 
 namespace {
 
-constexpr int kRedBlocks = 256;   // dot-product grids (k_dot_part)
 constexpr int kUpdBlocks = 1024;  // CG update grid cap: its r.r partials are re-summed by every direction block
 constexpr int kDirBlocks = 1024;  // CG direction grid cap
-constexpr int kCgBatch = 16;       // CG iterations per replayed graph (one host check per batch)
 
 // Device-side CG stop flags: flags[0] (every band stopped) makes every kernel of the
 // remaining enqueued iterations return at once, so iterations run as replayed
 // hipGraph batches with one host round trip per batch; flags[2+b] freezes band b.
 __device__ __forceinline__ bool cg_done(const int32_t *flags) { return flags && flags[0]; }
 __device__ __forceinline__ bool band_stopped(const int32_t *flags, int b) { return flags && flags[2 + b]; }
-
-// Fixed-order sum of n block partials by one 256-thread block (k_dot_final's order).
-// Each thread adds part[tid], part[tid + 256], ... in that order; the loads are issued
-// 8 at a time before the adds (a serial load -> add chain costs one L2 round trip per
-// partial: ~40 us for 4 bands x 2k partials at C4, most of the CG update kernel).
-__device__ __forceinline__ double block_final_sum(const double *__restrict__ part, int n, double *red)
-{
-    double acc = 0.0;
-    constexpr int kB = 8;
-    int i = threadIdx.x;
-    for (; i + (kB - 1) * 256 < n; i += kB * 256) {
-        double v[kB];
-#pragma unroll
-        for (int k = 0; k < kB; ++k) v[k] = part[i + k * 256];
-#pragma unroll
-        for (int k = 0; k < kB; ++k) acc += v[k];
-    }
-    for (; i < n; i += 256) acc += part[i];
-    acc = wave_sum(acc);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
 
 // block_final_sum for NB bands at once (band b's partials at part + b kPartMax): the
 // same per-band order and result, with every band's loads in flight together.
@@ -487,52 +461,6 @@ __global__ void __launch_bounds__(256) k_dot_final(const double *__restrict__ pa
     }
 }
 
-// one offset's x += a p ; r -= a q for the live bands, accumulating r.r (16-B vector access)
-template <int NB>
-__device__ __forceinline__ void update_row(double *__restrict__ x, double *__restrict__ r, const double *__restrict__ p,
-                                           const double *__restrict__ q, const double (&a)[NB], const bool (&live)[NB],
-                                           double (&acc)[NB])
-{
-    double xv[NB], rv[NB], pv[NB], qv[NB];
-    ldb<NB>(r, rv);
-    ldb<NB>(p, pv);
-    ldb<NB>(q, qv);
-    ldb<NB>(x, xv);
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-        if (live[b]) {
-            xv[b] += a[b] * pv[b];
-            rv[b] = rv[b] - a[b] * qv[b];
-        }
-        acc[b] = fma(rv[b], rv[b], acc[b]);
-    }
-    stb<NB>(x, xv);
-    stb<NB>(r, rv);
-}
-
-// p = r + beta p for the live bands of one offset; wbar != NULL (count form): also
-// pt = wbar o p, the next bin's input
-template <int NB>
-__device__ __forceinline__ void direction_row(double *__restrict__ p, const double *__restrict__ r,
-                                              const double (&beta)[NB], const bool (&live)[NB],
-                                              const double *__restrict__ wbar = nullptr, double *__restrict__ pt = nullptr)
-{
-    double pv[NB], rv[NB];
-    ldb<NB>(p, pv);
-    ldb<NB>(r, rv);
-#pragma unroll
-    for (int b = 0; b < NB; ++b)
-        if (live[b]) pv[b] = rv[b] + beta[b] * pv[b];
-    stb<NB>(p, pv);
-    if (wbar) {
-        double a[NB];
-        ldb<NB>(wbar, a);
-#pragma unroll
-        for (int b = 0; b < NB; ++b) pv[b] *= a[b];
-        stb<NB>(pt, pv);
-    }
-}
-
 // x += a p ; r -= a q ; a = rr / pq per band (bands already stopped are left alone);
 // per-band partials of r.r
 template <int NB>
@@ -794,6 +722,32 @@ int dot(comap_destriper *d, hipStream_t st, const double *a, const double *b, do
 }
 
 }  // namespace
+
+// ---- the launchers the ground solve shares (declared in destriper_internal.h; one band)
+void ds_launch_bin(const comap_destriper *d, hipStream_t st, const double *x, const double *base, const double *hdiv,
+                   double *num, const int32_t *flags, bool hit_rows, bool x_scaled)
+{
+    launch_bin(d, st, x, base, hdiv, num, flags, hit_rows, x_scaled);
+}
+
+void ds_launch_project(const comap_destriper *d, hipStream_t st, const double *x, const double *num, const double *h,
+                       double *y, const int32_t *flags)
+{
+    launch_project(d, st, x, num, h, y, nullptr, flags);
+}
+
+void ds_dot(comap_destriper *d, hipStream_t st, const double *a, const double *b, int64_t n, double *out)
+{
+    k_dot_part<1><<<kRedBlocks, 256, 0, st>>>(a, b, n, d->part);
+    k_dot_final<1><<<1, 256, 0, st>>>(d->part, kRedBlocks, out, nullptr);
+}
+
+void ds_dot_part(comap_destriper *d, hipStream_t st, const double *a, const double *b, int64_t n)
+{
+    k_dot_part<1><<<kRedBlocks, 256, 0, st>>>(a, b, n, d->part);
+}
+
+unsigned ds_upd_grid(int64_t NO) { return upd_grid(NO); }
 
 extern "C" int comap_destripe_destroy(comap_destriper *d)
 {
@@ -1058,19 +1012,30 @@ static bool cg_use_graph(const comap_destriper *d)
     return d->nnz + d->nnzp < 300000;
 }
 
-// CG state, stream and (small problems) the kCgBatch-iteration graph, created on first use.
-static int cg_setup(comap_destriper *d)
+// The CG stream, event, stop flags and pinned read-back blocks, created on first use (the ground
+// solve shares them and brings its own vectors).
+int ds_cg_state(comap_destriper *d)
 {
-    if (d->batch || (d->cs && !cg_use_graph(d))) return 0;
     comap_ctx *ctx = d->ctx;
     const size_t nb = (size_t)d->nb;
-    if (!d->cg && (dalloc(ctx, &d->cg, (4 * (size_t)d->NO + (size_t)d->npix) * nb) ||
-                   dalloc(ctx, &d->flags, 2 + 2 * nb)))
-        return -2;
+    if (!d->flags && dalloc(ctx, &d->flags, 2 + 2 * nb)) return -2;
     if (!d->flags_host) COMAP_CHECK(ctx, comap_pinned_alloc((void **)&d->flags_host, 4 * (2 + 2 * nb)));
     if (!d->thr_host) COMAP_CHECK(ctx, comap_pinned_alloc((void **)&d->thr_host, 8 * (1 + 4 * nb)));
     if (!d->cs) COMAP_CHECK(ctx, comap_stream_acquire(&d->cs));
     if (!d->ev) COMAP_CHECK(ctx, hipEventCreateWithFlags(&d->ev, hipEventDisableTiming));
+    return 0;
+}
+
+bool ds_cg_use_graph(const comap_destriper *d) { return cg_use_graph(d); }
+
+// CG vectors, state and (small problems) the kCgBatch-iteration graph, created on first use.
+static int cg_setup(comap_destriper *d)
+{
+    if (d->cg && (d->batch || !cg_use_graph(d))) return 0;
+    comap_ctx *ctx = d->ctx;
+    const size_t nb = (size_t)d->nb;
+    if (!d->cg && dalloc(ctx, &d->cg, (4 * (size_t)d->NO + (size_t)d->npix) * nb)) return -2;
+    if (const int rc = ds_cg_state(d)) return rc;
     if (!cg_use_graph(d)) return 0;
     hipGraph_t g = nullptr;
     COMAP_CHECK(ctx, hipStreamBeginCapture(d->cs, hipStreamCaptureModeThreadLocal));

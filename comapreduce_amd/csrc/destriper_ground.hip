@@ -24,6 +24,15 @@
 //     rhs:  b1_k = sum_{o in k} b_o,  ba_k = Ta_k - sum_e ga_e m_naive[read pixel of e]
 // The plain destriper's kernels are used through their C ABI, unchanged.
 //
+// Azimuth wrap.  A group whose raw azimuths span more than 180 degrees (max - min, pass 0; no scan
+// throws 180 degrees) crosses 0 / 360: every az < 180 of it is used as az + 360.0 wherever the
+// set-up reads az, so mu_k and sigma_k are those of the unwrapped series (mu_k may exceed 360) and
+// its level is relative to azimuth on [180, 540).  Other groups keep the raw values.
+//
+// comap_destripe_ground_solve (end of this file) runs the whole CG on the device: the same
+// launches per iteration on the problem's CG stream, gated by its device stop flag and replayed
+// kCgBatch at a time as a captured graph, with the eager driver's arithmetic bit for bit.
+//
 // Layout: (group, pixel) entries twice, as the offset<->pixel operator is -- group-major for the
 // projection (off-map reads kept with their negative pixel id, as opix) and pixel-major for the
 // bin (binned entries only).  Both come from one stable radix sort of the samples by (group, read
@@ -59,6 +68,11 @@ struct comap_ground {
     int64_t *chunks = nullptr;  // [nce + nco][3]
     int64_t *cgrp = nullptr;    // [2 (K + 1)] each group's entry-chunk range, then its offset-chunk range
     double *part = nullptr;     // [nce + 2 nco] chunk partials
+    int32_t *wrapped = nullptr; // [K] 1: the group crosses 0 / 360, its azimuths < 180 are used as az + 360
+    // device-resident CG of comap_destripe_ground_solve (fixed pointers: graph-replayable); the
+    // stream, scalars, stop flags and r.r partials are the plain problem's (d->cs, scal, flags, part)
+    double *cg = nullptr;       // [4 (NO + 2K) + NO + npix + 1]: x, r, p, q | x' | num | the tails' r.r
+    hipGraphExec_t batch = nullptr;   // kCgBatch iterations
 };
 
 namespace {
@@ -122,24 +136,31 @@ __global__ void k_gr_rowptr(const int32_t *__restrict__ skey, int64_t n, int64_t
         row[k] = lb32(skey, n, k);
 }
 
+// The azimuth of a sample as the set-up uses it: a group that crosses 0 / 360 (wr) has its
+// values below 180 moved up one turn -- one f64 add, before any arithmetic on the value.
+__device__ __forceinline__ double unwrap_az(double v, bool wr) { return (wr && v < 180.0) ? v + 360.0 : v; }
+
 // Per-offset sums over its L samples in sample order, a thread per internal offset i (offset
 // perm[i]).  PASS 0: sum az, min, max.  PASS 1: sum (az - mu)^2.  PASS 2: sum w a, sum w a^2,
-// sum w a tod with a = (az - mu) / sigma (0 when sigma == 0).
+// sum w a tod with a = (az - mu) / sigma (0 when sigma == 0).  wrapped (NULL in the first pass 0,
+// which finds the flags): the groups whose azimuths are unwrapped.
 template <int PASS>
 __global__ void __launch_bounds__(256) k_gr_offsets(const double *__restrict__ az, const double *__restrict__ w,
                                                     const double *__restrict__ tod, const int32_t *__restrict__ perm,
                                                     const int32_t *__restrict__ gint, const double *__restrict__ mu,
-                                                    const double *__restrict__ sigma, int64_t NO, int L,
+                                                    const double *__restrict__ sigma,
+                                                    const int32_t *__restrict__ wrapped, int64_t NO, int L,
                                                     double *__restrict__ o0, double *__restrict__ o1,
                                                     double *__restrict__ o2)
 {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < NO; i += (int64_t)gridDim.x * blockDim.x) {
         const int64_t t0 = (int64_t)perm[i] * L;
         const int32_t k = gint[i];
+        const bool wr = wrapped && wrapped[k];
         if constexpr (PASS == 0) {
-            double s = 0.0, mn = az[t0], mx = az[t0];
+            double s = 0.0, mn = unwrap_az(az[t0], wr), mx = mn;
             for (int j = 0; j < L; ++j) {
-                const double v = az[t0 + j];
+                const double v = unwrap_az(az[t0 + j], wr);
                 s += v;
                 mn = fmin(mn, v);
                 mx = fmax(mx, v);
@@ -149,7 +170,7 @@ __global__ void __launch_bounds__(256) k_gr_offsets(const double *__restrict__ a
             const double m = mu[k];
             double s = 0.0;
             for (int j = 0; j < L; ++j) {
-                const double v = az[t0 + j] - m;
+                const double v = unwrap_az(az[t0 + j], wr) - m;
                 s = fma(v, v, s);
             }
             o0[i] = s;
@@ -157,7 +178,7 @@ __global__ void __launch_bounds__(256) k_gr_offsets(const double *__restrict__ a
             const double m = mu[k], sg = sigma[k];
             double sa = 0.0, saa = 0.0, sat = 0.0;
             for (int j = 0; j < L; ++j) {
-                const double a = sg > 0.0 ? (az[t0 + j] - m) / sg : 0.0;
+                const double a = sg > 0.0 ? (unwrap_az(az[t0 + j], wr) - m) / sg : 0.0;
                 const double wv = w[t0 + j] * a;
                 sa += wv;
                 saa = fma(wv, a, saa);
@@ -205,6 +226,15 @@ __global__ void k_gr_mean(const double *__restrict__ sum, const int64_t *__restr
         const int64_t n = (grow[k + 1] - grow[k]) * L;
         mu[k] = n ? sum[k] / (double)n : 0.0;
     }
+}
+
+// wrapped[k] = the group's raw azimuths span more than 180 degrees: it crosses 0 / 360 (no scan
+// throws 180 degrees)
+__global__ void k_gr_wrapflag(const double *__restrict__ mn, const double *__restrict__ mx,
+                              const int64_t *__restrict__ grow, int64_t K, int32_t *__restrict__ wrapped)
+{
+    for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < K; k += (int64_t)gridDim.x * blockDim.x)
+        wrapped[k] = (grow[k + 1] > grow[k] && mx[k] - mn[k] > 180.0) ? 1 : 0;
 }
 
 // sigma_k = sqrt(sum (az - mu)^2 / n); exactly 0 for an empty group or a constant azimuth
@@ -255,7 +285,8 @@ __global__ void __launch_bounds__(256) k_gr_entries(const uint64_t *__restrict__
                                                     const int32_t *__restrict__ estart, int64_t ne, int64_t N,
                                                     int64_t npix, const double *__restrict__ az,
                                                     const double *__restrict__ w, const double *__restrict__ mu,
-                                                    const double *__restrict__ sigma, int32_t *__restrict__ egrp,
+                                                    const double *__restrict__ sigma,
+                                                    const int32_t *__restrict__ wrapped, int32_t *__restrict__ egrp,
                                                     int32_t *__restrict__ gpix, double *__restrict__ ga,
                                                     int32_t *__restrict__ pkey, int32_t *__restrict__ pval)
 {
@@ -265,10 +296,11 @@ __global__ void __launch_bounds__(256) k_gr_entries(const uint64_t *__restrict__
         const bool off = key & 1u;
         const int64_t k = (int64_t)((key >> 1) / (uint64_t)npix), q = (int64_t)((key >> 1) % (uint64_t)npix);
         const double m = mu[k], sg = sigma[k];
+        const bool wr = wrapped[k] != 0;
         double acc = 0.0;
         for (int64_t i = i0; i < i1; ++i) {
             const int64_t t = sval[i];
-            const double a = sg > 0.0 ? (az[t] - m) / sg : 0.0;
+            const double a = sg > 0.0 ? (unwrap_az(az[t], wr) - m) / sg : 0.0;
             acc += w[t] * a;
         }
         egrp[e] = (int32_t)k;
@@ -293,26 +325,37 @@ __global__ void k_gr_pixel_entries(const int32_t *__restrict__ spkey, const int3
 }
 
 // ---------------------------------------------------------------- per-iteration kernels
-// x'_i = x_i + c_{g(i)}
+// The native solve's kernels return at once when the CG's device stop flag is set (flags[0],
+// destriper_internal.h); the per-piece C ABI passes flags == NULL.
+__device__ __forceinline__ bool gr_done(const int32_t *flags) { return flags && flags[0]; }
+
+// x'_i = x_i + c_{g(i)}; wbar != NULL (the count form's bin input): also pt_i = wbar_i x'_i
 __global__ void k_gr_fold(const double *__restrict__ x, const double *__restrict__ c, const int32_t *__restrict__ gint,
-                          int64_t NO, double *__restrict__ xp)
+                          int64_t NO, double *__restrict__ xp, const double *__restrict__ wbar,
+                          double *__restrict__ pt, const int32_t *__restrict__ flags)
 {
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < NO; i += (int64_t)gridDim.x * blockDim.x)
-        xp[i] = x[i] + c[gint[i]];
+    if (gr_done(flags)) return;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < NO; i += (int64_t)gridDim.x * blockDim.x) {
+        const double v = x[i] + c[gint[i]];
+        xp[i] = v;
+        if (wbar) pt[i] = wbar[i] * v;
+    }
 }
 
-// num_p += sum_{e in pixel row p} ga_e s_{k(e)}: a gather per pixel row, kBinLanes lanes per row
-// (lane-strided, then the lanes' sums); rows without entries are not written.
+// num_p += sum_{e in pixel row p} ga_e (sign s_{k(e)}), sign = +-1: a gather per pixel row,
+// kBinLanes lanes per row (lane-strided, then the lanes' sums); rows without entries are not written.
 __global__ void __launch_bounds__(256) k_gr_bin(const int64_t *__restrict__ gprow, const int32_t *__restrict__ gpk,
                                                 const double *__restrict__ gpa, const double *__restrict__ s,
-                                                int64_t npix, double *__restrict__ num)
+                                                double sign, int64_t npix, double *__restrict__ num,
+                                                const int32_t *__restrict__ flags)
 {
+    if (gr_done(flags)) return;
     const int sub = threadIdx.x & (kBinLanes - 1);
     const int64_t step = (int64_t)gridDim.x * blockDim.x / kBinLanes;
     for (int64_t p = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kBinLanes; p < npix; p += step) {
         const int64_t e0 = gprow[p], e1 = gprow[p + 1];
         double acc = 0.0;
-        for (int64_t j = e0 + sub; j < e1; j += kBinLanes) acc = fma(gpa[j], s[gpk[j]], acc);
+        for (int64_t j = e0 + sub; j < e1; j += kBinLanes) acc = fma(gpa[j], sign * s[gpk[j]], acc);
 #pragma unroll
         for (int o = kBinLanes / 2; o > 0; o >>= 1) acc += __shfl_xor(acc, o, kBinLanes);
         if (sub == 0 && e1 > e0) num[p] += acc;
@@ -329,9 +372,10 @@ __global__ void __launch_bounds__(256) k_gr_parts(const int64_t *__restrict__ ch
                                                   int64_t npix, const int32_t *__restrict__ glist,
                                                   const double *__restrict__ wa, const double *__restrict__ xp,
                                                   const double *__restrict__ s, double *__restrict__ y,
-                                                  double *__restrict__ part)
+                                                  double *__restrict__ part, const int32_t *__restrict__ flags)
 {
     __shared__ double red[4];
+    if (gr_done(flags)) return;
     const int64_t c = blockIdx.x;
     const int64_t k = chunks[3 * c], b = chunks[3 * c + 1], e = chunks[3 * c + 2];
     if (c < nce) {
@@ -382,8 +426,9 @@ __global__ void __launch_bounds__(256) k_gr_parts(const int64_t *__restrict__ ch
 __global__ void __launch_bounds__(64) k_gr_finish(const int64_t *__restrict__ cgrp, int64_t K, int64_t nce,
                                                   const double *__restrict__ part, const double *__restrict__ saa,
                                                   const double *__restrict__ ta, const double *__restrict__ s,
-                                                  double *__restrict__ z)
+                                                  double *__restrict__ z, const int32_t *__restrict__ flags)
 {
+    if (gr_done(flags)) return;
     const int64_t k = blockIdx.x;
     double ae = 0.0, a1 = 0.0, aa = 0.0;
     for (int64_t c = cgrp[k] + threadIdx.x; c < cgrp[k + 1]; c += 64) ae += part[c];
@@ -402,14 +447,21 @@ __global__ void __launch_bounds__(64) k_gr_finish(const int64_t *__restrict__ cg
 
 // The CG's vector algebra on the 2K-value tails (s | c), one workgroup each; the offsets' part of
 // every vector runs through the plain problem's kernels.  Sums are fixed-order.
+// a . b over n tail values by one block: thread-strided fmas, then the block
+__device__ __forceinline__ double tail_dot(const double *__restrict__ a, const double *__restrict__ b, int64_t n,
+                                           double *red)
+{
+    double acc = 0.0;
+    for (int64_t i = threadIdx.x; i < n; i += 256) acc = fma(a[i], b[i], acc);
+    return block_sum(acc, red);
+}
+
 // out += a . b
 __global__ void __launch_bounds__(256) k_gr_tail_dot(const double *__restrict__ a, const double *__restrict__ b,
                                                      int64_t n, double *__restrict__ out)
 {
     __shared__ double red[4];
-    double acc = 0.0;
-    for (int64_t i = threadIdx.x; i < n; i += 256) acc = fma(a[i], b[i], acc);
-    acc = block_sum(acc, red);
+    const double acc = tail_dot(a, b, n, red);
     if (threadIdx.x == 0) out[0] += acc;
 }
 
@@ -441,10 +493,89 @@ __global__ void __launch_bounds__(256) k_gr_tail_direction(const double *__restr
     for (int64_t i = threadIdx.x; i < n; i += 256) p[i] = r[i] + beta * p[i];
 }
 
+// out_p = num_p / h_p (num_p where h_p == 0)
+__global__ void k_gr_div(const double *__restrict__ num, const double *__restrict__ h, int64_t n,
+                         double *__restrict__ out)
+{
+    for (int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; p < n; p += (int64_t)gridDim.x * blockDim.x)
+        out[p] = map_value(num, h, p);
+}
+
+// The native solve's update and direction over whole vectors [x | s | c]: the arithmetic and the
+// summation orders of the eager driver's calls -- comap_destripe_dot / _cg_update / _cg_direction
+// on the NO offsets, then the one-workgroup tail kernels above on the 2K tail values -- so the
+// iterates equal the eager driver's bit for bit (the operator has a null space, and CG on it
+// magnifies a rounding difference by many orders of magnitude within some iterations), folded
+// into two gated launches.  Every block re-derives the sums from the partials in the same fixed
+// order, so all hold identical values; block 0 also advances the tails.
+//   k_gr_update: p.q = sum(part_pq, k_dot_part's partials of the offsets) + the tails' p.q;
+//       a = rr / p.q; x += a p; r -= a q; r.r partials of the offsets into part_rr (k_cg_update's
+//       grid), the tails' r.r into tail_rr; block 0 saves rr and p.q
+__global__ void __launch_bounds__(256) k_gr_update(double *__restrict__ scal, const double *__restrict__ part_pq,
+                                                   double *__restrict__ x, double *__restrict__ r,
+                                                   const double *__restrict__ p, const double *__restrict__ q,
+                                                   int64_t NO, int64_t K, double *__restrict__ part_rr,
+                                                   double *__restrict__ tail_rr, const int32_t *__restrict__ flags)
+{
+    __shared__ double red[4];
+    if (gr_done(flags)) return;
+    double pq = block_final_sum(part_pq, kRedBlocks, red);
+    pq += tail_dot(p + NO, q + NO, 2 * K, red);
+    const double rr = scal[3];
+    const double a[1] = {rr / pq};
+    const bool live[1] = {true};
+    double acc[1] = {0.0};
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < NO; i += (int64_t)gridDim.x * blockDim.x)
+        update_row<1>(x + i, r + i, p + i, q + i, a, live, acc);
+    const double bs = block_sum(acc[0], red);
+    if (threadIdx.x == 0) part_rr[blockIdx.x] = bs;
+    if (blockIdx.x == 0) {
+        const double alpha = a[0];
+        double t = 0.0;
+        for (int64_t i = NO + threadIdx.x; i < NO + 2 * K; i += 256) {
+            x[i] += alpha * p[i];
+            const double rv = r[i] - alpha * q[i];
+            r[i] = rv;
+            t = fma(rv, rv, t);
+        }
+        t = block_sum(t, red);
+        if (threadIdx.x == 0) { tail_rr[0] = t; scal[1] = rr; scal[2] = pq; }
+    }
+}
+
+//   k_gr_direction: rr_new = sum(part_rr) + tail_rr; p = r + (rr_new / rr) p; block 0, after its
+//       own sweep: rr = rr_new, count the iteration, stop when rr_new / rr0 is NaN or below the
+//       threshold (scal / flags: the one-band layout of destriper_internal.h)
+__global__ void __launch_bounds__(256) k_gr_direction(double *__restrict__ scal, const double *__restrict__ part_rr,
+                                                      int nrr, const double *__restrict__ tail_rr,
+                                                      double *__restrict__ p, const double *__restrict__ r, int64_t NO,
+                                                      int64_t K, int32_t *flags)
+{
+    __shared__ double red[4];
+    if (flags[0]) return;
+    double rrn = block_final_sum(part_rr, nrr, red);
+    rrn += tail_rr[0];
+    const double beta[1] = {rrn / scal[1]};
+    const bool live[1] = {true};
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < NO; i += (int64_t)gridDim.x * blockDim.x)
+        direction_row<1>(p + i, r + i, beta, live);
+    if (blockIdx.x == 0) {
+        for (int64_t i = NO + threadIdx.x; i < NO + 2 * K; i += 256) p[i] = r[i] + beta[0] * p[i];
+        if (threadIdx.x == 0) {
+            scal[3] = rrn;
+            flags[3] += 1;
+            flags[1] += 1;
+            const double delta = rrn / scal[0];
+            if (isnan(delta) || delta < scal[4]) { flags[2] = 1; flags[0] = 1; }
+        }
+    }
+}
+
 void ground_free(comap_ground *g, bool idle)
 {
+    if (g->batch) (void)hipGraphExecDestroy(g->batch);
     void *b[] = {g->gint, g->glist, g->wa, g->mu, g->sigma, g->saa, g->ta, g->gpix, g->ga, g->gprow, g->gpk, g->gpa,
-                 g->chunks, g->cgrp, g->part};
+                 g->chunks, g->cgrp, g->part, g->wrapped, g->cg};
     comap_tmp_free_on(b, (int)(sizeof(b) / sizeof(b[0])), nullptr, idle);
     delete g;
 }
@@ -465,6 +596,7 @@ int ground_build(comap_ground *g, const int32_t *pix, const double *az, const do
     rc |= dalloc(ctx, &g->sigma, K);
     rc |= dalloc(ctx, &g->saa, K);
     rc |= dalloc(ctx, &g->ta, K);
+    rc |= dalloc(ctx, &g->wrapped, K);
     rc |= dalloc(ctx, &g->gprow, npix + 1);
     rc |= dalloc(ctx, &g->cgrp, 2 * (K + 1));
     if (rc) return -2;
@@ -517,16 +649,26 @@ int ground_build(comap_ground *g, const int32_t *pix, const double *az, const do
     COMAP_LAUNCH_CHECK(ctx);
 
     // ---- 2. mu, sigma per group; wa per offset; Saa, Ta per group
+    // (pass 0 twice: on the raw azimuths for each group's span, hence its wrap flag, then on the
+    // unwrapped values -- for a group that is not flagged the same arithmetic on the same values)
     double *o0 = ov, *o1 = ov + NO, *o2 = ov + 2 * NO;
-    k_gr_offsets<0><<<grid_for(NO), 256, 0, st>>>(az, w, tod, d->perm, g->gint, nullptr, nullptr, NO, L, o0, o1, o2);
+    k_gr_offsets<0><<<grid_for(NO), 256, 0, st>>>(az, w, tod, d->perm, g->gint, nullptr, nullptr, nullptr, NO, L, o0,
+                                                  o1, o2);
+    k_gr_group<1><<<(unsigned)K, 256, 0, st>>>(o1, g->glist, grow, gv + K);
+    k_gr_group<2><<<(unsigned)K, 256, 0, st>>>(o2, g->glist, grow, gv + 2 * K);
+    k_gr_wrapflag<<<grid_for(K), 256, 0, st>>>(gv + K, gv + 2 * K, grow, K, g->wrapped);
+    k_gr_offsets<0><<<grid_for(NO), 256, 0, st>>>(az, w, tod, d->perm, g->gint, nullptr, nullptr, g->wrapped, NO, L,
+                                                  o0, o1, o2);
     k_gr_group<0><<<(unsigned)K, 256, 0, st>>>(o0, g->glist, grow, gv);
     k_gr_group<1><<<(unsigned)K, 256, 0, st>>>(o1, g->glist, grow, gv + K);
     k_gr_group<2><<<(unsigned)K, 256, 0, st>>>(o2, g->glist, grow, gv + 2 * K);
     k_gr_mean<<<grid_for(K), 256, 0, st>>>(gv, grow, K, L, g->mu);
-    k_gr_offsets<1><<<grid_for(NO), 256, 0, st>>>(az, w, tod, d->perm, g->gint, g->mu, nullptr, NO, L, o0, o1, o2);
+    k_gr_offsets<1><<<grid_for(NO), 256, 0, st>>>(az, w, tod, d->perm, g->gint, g->mu, nullptr, g->wrapped, NO, L, o0,
+                                                  o1, o2);
     k_gr_group<0><<<(unsigned)K, 256, 0, st>>>(o0, g->glist, grow, gv);
     k_gr_rms<<<grid_for(K), 256, 0, st>>>(gv, gv + K, gv + 2 * K, grow, K, L, g->sigma);
-    k_gr_offsets<2><<<grid_for(NO), 256, 0, st>>>(az, w, tod, d->perm, g->gint, g->mu, g->sigma, NO, L, g->wa, o1, o2);
+    k_gr_offsets<2><<<grid_for(NO), 256, 0, st>>>(az, w, tod, d->perm, g->gint, g->mu, g->sigma, g->wrapped, NO, L,
+                                                  g->wa, o1, o2);
     k_gr_group<0><<<(unsigned)K, 256, 0, st>>>(o1, g->glist, grow, g->saa);
     k_gr_group<0><<<(unsigned)K, 256, 0, st>>>(o2, g->glist, grow, g->ta);
     COMAP_LAUNCH_CHECK(ctx);
@@ -562,8 +704,8 @@ int ground_build(comap_ground *g, const int32_t *pix, const double *az, const do
     COMAP_CHECK(ctx, tmp.alloc(&pkey, ne));
     COMAP_CHECK(ctx, tmp.alloc(&spkey, ne));
     // (val / sval are free again: the pixel-major sort's values)
-    k_gr_entries<<<grid_for(ne, 65536), 256, 0, st>>>(skey, sval, estart, ne, N, npix, az, w, g->mu, g->sigma, egrp,
-                                                      g->gpix, g->ga, pkey, val);
+    k_gr_entries<<<grid_for(ne, 65536), 256, 0, st>>>(skey, sval, estart, ne, N, npix, az, w, g->mu, g->sigma,
+                                                      g->wrapped, egrp, g->gpix, g->ga, pkey, val);
     k_gr_rowptr<<<grid_for(K + 1), 256, 0, st>>>(egrp, ne, K, garow);
     COMAP_LAUNCH_CHECK(ctx);
     int32_t *spval = estart;               // (the segment starts are consumed)
@@ -678,8 +820,17 @@ extern "C" int comap_destripe_ground_fold(comap_ground *g, const double *x, cons
     if (!g || !x || !c || !xprime) return -1;
     COMAP_DEVICE_GUARD(g->ctx);
     comap_ctx *ctx = g->ctx;
-    k_gr_fold<<<grid_for(g->NO), 256, 0, ctx->stream>>>(x, c, g->gint, g->NO, xprime);
+    k_gr_fold<<<grid_for(g->NO), 256, 0, ctx->stream>>>(x, c, g->gint, g->NO, xprime, nullptr, nullptr, nullptr);
     COMAP_LAUNCH_CHECK(ctx);
+    return 0;
+}
+
+extern "C" int comap_destripe_ground_wrapped(comap_ground *g, int32_t *flag)
+{
+    if (!g || !flag) return -1;
+    COMAP_DEVICE_GUARD(g->ctx);
+    comap_ctx *ctx = g->ctx;
+    COMAP_CHECK(ctx, hipMemcpyAsync(flag, g->wrapped, 4 * (size_t)g->K, hipMemcpyDeviceToDevice, ctx->stream));
     return 0;
 }
 
@@ -688,9 +839,21 @@ extern "C" int comap_destripe_ground_bin(comap_ground *g, const double *s, doubl
     if (!g || !s || !num) return -1;
     COMAP_DEVICE_GUARD(g->ctx);
     comap_ctx *ctx = g->ctx;
-    k_gr_bin<<<grid_for(g->npix * kBinLanes, 65536), 256, 0, ctx->stream>>>(g->gprow, g->gpk, g->gpa, s, g->npix, num);
+    k_gr_bin<<<grid_for(g->npix * kBinLanes, 65536), 256, 0, ctx->stream>>>(g->gprow, g->gpk, g->gpa, s, 1.0, g->npix,
+                                                                            num, nullptr);
     COMAP_LAUNCH_CHECK(ctx);
     return 0;
+}
+
+// The ground projection on stream st (flags: the native solve's stop flags, or NULL)
+static void launch_ground_project(comap_ground *g, hipStream_t st, const double *xprime, const double *s,
+                                  const double *num, const double *h, double *y, double *z, const int32_t *flags)
+{
+    const int64_t nc = g->nce + g->nco;
+    if (nc)
+        k_gr_parts<<<(unsigned)nc, 256, 0, st>>>(g->chunks, g->nce, g->gpix, g->ga, num, h, g->npix, g->glist, g->wa,
+                                                 xprime, s, y, g->part, flags);
+    k_gr_finish<<<(unsigned)g->K, 64, 0, st>>>(g->cgrp, g->K, g->nce, g->part, g->saa, g->ta, s, z, flags);
 }
 
 static int ground_project(comap_ground *g, const double *xprime, const double *s, const double *num, const double *h,
@@ -698,11 +861,7 @@ static int ground_project(comap_ground *g, const double *xprime, const double *s
 {
     COMAP_DEVICE_GUARD(g->ctx);
     comap_ctx *ctx = g->ctx;
-    const int64_t nc = g->nce + g->nco;
-    if (nc)
-        k_gr_parts<<<(unsigned)nc, 256, 0, ctx->stream>>>(g->chunks, g->nce, g->gpix, g->ga, num, h ? h : g->d->h,
-                                                          g->npix, g->glist, g->wa, xprime, s, y, g->part);
-    k_gr_finish<<<(unsigned)g->K, 64, 0, ctx->stream>>>(g->cgrp, g->K, g->nce, g->part, g->saa, g->ta, s, z);
+    launch_ground_project(g, ctx->stream, xprime, s, num, h ? h : g->d->h, y, z, nullptr);
     COMAP_LAUNCH_CHECK(ctx);
     return 0;
 }
@@ -750,5 +909,119 @@ extern "C" int comap_destripe_ground_tail_direction(comap_ground *g, const doubl
     comap_ctx *ctx = g->ctx;
     k_gr_tail_direction<<<1, 256, 0, ctx->stream>>>(rr_new, rr, p, r, 2 * g->K);
     COMAP_LAUNCH_CHECK(ctx);
+    return 0;
+}
+
+// ---------------------------------------------------------------- device-resident ground CG
+// One CG iteration on the ground object's own vectors u = [x | s | c] (n = NO + 2K values each):
+// the launches of the eager driver's iteration with their arguments -- fold, bin (undivided; m =
+// num / h on the fly in the projection and in k_gr_parts), ground bin, projection, ground
+// projection, the offsets' p.q partials on the finished q -- and its dot finals, update, tail
+// update, direction, tail direction and stop test folded into k_gr_update / k_gr_direction.
+// 9 launches (the count form's scaling rides in the fold), all but the partials' gated by the
+// stop flag; the iterates are the eager driver's bit for bit.
+static void ground_enqueue_iteration(comap_ground *g, hipStream_t st)
+{
+    comap_destriper *d = g->d;
+    const int64_t NO = g->NO, K = g->K, n = NO + 2 * K;
+    double *x = g->cg, *r = x + n, *p = r + n, *q = p + n, *xp = q + n, *num = xp + NO, *tail_rr = num + g->npix;
+    int32_t *flags = d->flags;
+    double *part_rr = d->part + kPartMax;
+    // x' = p + c[g(o)] (count form: and the bin's input pt = wbar o x')
+    k_gr_fold<<<grid_for(NO), 256, 0, st>>>(p, p + NO + K, g->gint, NO, xp, d->cf ? d->wbar : nullptr, d->pt, flags);
+    // (every row, as comap_destripe_bin: the hit-row bin sizes its lanes differently, another summation order)
+    ds_launch_bin(d, st, d->cf ? d->pt : xp, nullptr, nullptr, num, flags, false, d->cf);
+    k_gr_bin<<<grid_for(g->npix * kBinLanes, 65536), 256, 0, st>>>(g->gprow, g->gpk, g->gpa, p + NO, 1.0, g->npix, num,
+                                                                   flags);
+    ds_launch_project(d, st, xp, num, d->h, q, flags);
+    launch_ground_project(g, st, xp, p + NO, num, d->h, q, q + NO, flags);
+    ds_dot_part(d, st, p, q, NO);   // not gated: it writes the partials only
+    const unsigned ug = ds_upd_grid(NO);
+    k_gr_update<<<ug, 256, 0, st>>>(d->scal, d->part, x, r, p, q, NO, K, part_rr, tail_rr, flags);
+    k_gr_direction<<<grid_for(NO), 256, 0, st>>>(d->scal, part_rr, (int)ug, tail_rr, p, r, NO, K, flags);
+}
+
+// CG vectors and (small problems, or COMAP_DS_CGGRAPH=1) the kCgBatch-iteration graph, on first use
+static int ground_cg_setup(comap_ground *g)
+{
+    comap_destriper *d = g->d;
+    comap_ctx *ctx = g->ctx;
+    if (g->cg && (g->batch || !ds_cg_use_graph(d))) return 0;
+    const int64_t n = g->NO + 2 * g->K;
+    if (!g->cg && dalloc(ctx, &g->cg, 4 * (size_t)n + (size_t)g->NO + (size_t)g->npix + 1)) return -2;
+    if (const int rc = ds_cg_state(d)) return rc;
+    if (!ds_cg_use_graph(d)) return 0;
+    // (the vectors were allocated in the context stream's order: the capture below only records)
+    hipGraph_t gr = nullptr;
+    COMAP_CHECK(ctx, hipStreamBeginCapture(d->cs, hipStreamCaptureModeThreadLocal));
+    for (int i = 0; i < kCgBatch; ++i) ground_enqueue_iteration(g, d->cs);
+    COMAP_CHECK(ctx, hipStreamEndCapture(d->cs, &gr));
+    const hipError_t e = hipGraphInstantiate(&g->batch, gr, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(gr);
+    COMAP_CHECK(ctx, e);
+    return 0;
+}
+
+// cg_solve(GroundOps, identity, threshold, niter) without Python per iteration: kCgBatch iterations
+// per graph launch and host check, a remainder below kCgBatch as plain launches; the device stop
+// flag makes the iterations queued behind convergence no-ops.  Then the maps, as _solve_ground.
+extern "C" int comap_destripe_ground_solve(comap_ground *g, double threshold, int32_t niter, double *u, double *map,
+                                           double *naive, double *weight, double *hits, int32_t *iters_out)
+{
+    if (!g || !u || niter < 0) return -1;
+    COMAP_DEVICE_GUARD(g->ctx);
+    comap_ctx *ctx = g->ctx;
+    comap_destriper *d = g->d;
+    int rc = ground_cg_setup(g);
+    if (rc) return rc;
+    hipStream_t st = d->cs;
+    const int64_t NO = g->NO, K = g->K, n = NO + 2 * K, np = g->npix;
+    double *x = g->cg, *r = x + n, *p = r + n, *xp = p + 2 * n, *num = xp + NO;
+    // inputs (and the vectors' allocation) are ordered on the caller's stream
+    COMAP_CHECK(ctx, hipEventRecord(d->ev, ctx->stream));
+    COMAP_CHECK(ctx, hipStreamWaitEvent(st, d->ev, 0));
+    d->thr_host[0] = threshold;
+    COMAP_CHECK(ctx, hipMemcpyAsync(d->scal + 4, d->thr_host, 8, hipMemcpyHostToDevice, st));
+    COMAP_CHECK(ctx, hipMemsetAsync(x, 0, 8 * (size_t)n, st));
+    COMAP_CHECK(ctx, hipMemsetAsync(d->flags, 0, 4 * 4, st));
+    // b: the offsets' rows, then the tail from them; r = p = b (u0 = 0); rr = rr0 = b.b
+    ds_launch_project(d, st, nullptr, d->nnum, d->h, r, nullptr);
+    launch_ground_project(g, st, nullptr, nullptr, d->nnum, d->h, r, r + NO, nullptr);
+    COMAP_LAUNCH_CHECK(ctx);
+    COMAP_CHECK(ctx, hipMemcpyAsync(p, r, 8 * (size_t)n, hipMemcpyDeviceToDevice, st));
+    ds_dot(d, st, r, r, NO, d->scal);
+    k_gr_tail_dot<<<1, 256, 0, st>>>(r + NO, r + NO, 2 * K, d->scal);
+    COMAP_LAUNCH_CHECK(ctx);
+    COMAP_CHECK(ctx, hipMemcpyAsync(d->scal + 1, d->scal, 8, hipMemcpyDeviceToDevice, st));
+    COMAP_CHECK(ctx, hipMemcpyAsync(d->scal + 3, d->scal, 8, hipMemcpyDeviceToDevice, st));   // current rr
+    for (int i = 0; i < 4; ++i) d->flags_host[i] = 0;
+    for (int enq = 0; enq < niter;) {
+        const int k = std::min(kCgBatch, niter - enq);
+        if (k == kCgBatch && g->batch) {
+            COMAP_CHECK(ctx, hipGraphLaunch(g->batch, st));
+        } else {
+            for (int i = 0; i < k; ++i) ground_enqueue_iteration(g, st);
+            COMAP_LAUNCH_CHECK(ctx);
+        }
+        enq += k;
+        COMAP_CHECK(ctx, hipMemcpyAsync(d->flags_host, d->flags, 4 * 4, hipMemcpyDeviceToHost, st));
+        COMAP_CHECK(ctx, hipStreamSynchronize(st));
+        if (d->flags_host[0]) break;
+    }
+    if (iters_out) iters_out[0] = d->flags_host[3];
+    COMAP_CHECK(ctx, hipMemcpyAsync(u, x, 8 * (size_t)n, hipMemcpyDeviceToDevice, st));
+    // final maps: map = (sum w tod - W x' - ground bin(s)) / h ; naive = sum w tod / h
+    if (map) {
+        k_gr_fold<<<grid_for(NO), 256, 0, st>>>(x, x + NO + K, g->gint, NO, xp, nullptr, nullptr, nullptr);
+        ds_launch_bin(d, st, xp, d->nnum, nullptr, num, nullptr, false, false);
+        k_gr_bin<<<grid_for(np * kBinLanes, 65536), 256, 0, st>>>(g->gprow, g->gpk, g->gpa, x + NO, -1.0, np, num,
+                                                                  nullptr);
+        k_gr_div<<<grid_for(np), 256, 0, st>>>(num, d->h, np, map);
+    }
+    if (naive) k_gr_div<<<grid_for(np), 256, 0, st>>>(d->nnum, d->h, np, naive);
+    COMAP_LAUNCH_CHECK(ctx);
+    if (weight) COMAP_CHECK(ctx, hipMemcpyAsync(weight, d->h, 8 * (size_t)np, hipMemcpyDeviceToDevice, st));
+    if (hits) COMAP_CHECK(ctx, hipMemcpyAsync(hits, d->hits, 8 * (size_t)np, hipMemcpyDeviceToDevice, st));
+    COMAP_CHECK(ctx, hipStreamSynchronize(st));
     return 0;
 }

@@ -127,6 +127,8 @@ struct comap_destriper {
 constexpr int kProjU = 4;         // entry loads in flight per k_ds_project lane
 constexpr int kProjBlocks = 1024; // k_ds_project grid cap: its p.q partials are re-summed by every update block
 constexpr int kPartMax = 8192;     // >= every reduction grid of the CG unit
+constexpr int kRedBlocks = 256;    // dot-product grids (k_dot_part)
+constexpr int kCgBatch = 16;       // CG iterations per replayed graph (one host check per batch)
 constexpr int64_t kSellMinOffsets = 131072;   // sliced-ELLPACK projection by default from this many offsets
 constexpr int32_t kSellPad = (int32_t)0x80808080;   // memset pattern 0x80: a padding slot
 
@@ -200,6 +202,76 @@ __device__ __forceinline__ double wave_sum(double v)
     return v;
 }
 
+// Fixed-order sum of n block partials by one 256-thread block (k_dot_final's order).
+// Each thread adds part[tid], part[tid + 256], ... in that order; the loads are issued
+// 8 at a time before the adds (a serial load -> add chain costs one L2 round trip per
+// partial: ~40 us for 4 bands x 2k partials at C4, most of the CG update kernel).
+__device__ __forceinline__ double block_final_sum(const double *__restrict__ part, int n, double *red)
+{
+    double acc = 0.0;
+    constexpr int kB = 8;
+    int i = threadIdx.x;
+    for (; i + (kB - 1) * 256 < n; i += kB * 256) {
+        double v[kB];
+#pragma unroll
+        for (int k = 0; k < kB; ++k) v[k] = part[i + k * 256];
+#pragma unroll
+        for (int k = 0; k < kB; ++k) acc += v[k];
+    }
+    for (; i < n; i += 256) acc += part[i];
+    acc = wave_sum(acc);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// one offset's x += a p ; r -= a q for the live bands, accumulating r.r (16-B vector access)
+template <int NB>
+__device__ __forceinline__ void update_row(double *__restrict__ x, double *__restrict__ r, const double *__restrict__ p,
+                                           const double *__restrict__ q, const double (&a)[NB], const bool (&live)[NB],
+                                           double (&acc)[NB])
+{
+    double xv[NB], rv[NB], pv[NB], qv[NB];
+    ldb<NB>(r, rv);
+    ldb<NB>(p, pv);
+    ldb<NB>(q, qv);
+    ldb<NB>(x, xv);
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        if (live[b]) {
+            xv[b] += a[b] * pv[b];
+            rv[b] = rv[b] - a[b] * qv[b];
+        }
+        acc[b] = fma(rv[b], rv[b], acc[b]);
+    }
+    stb<NB>(x, xv);
+    stb<NB>(r, rv);
+}
+
+// p = r + beta p for the live bands of one offset; wbar != NULL (count form): also
+// pt = wbar o p, the next bin's input
+template <int NB>
+__device__ __forceinline__ void direction_row(double *__restrict__ p, const double *__restrict__ r,
+                                              const double (&beta)[NB], const bool (&live)[NB],
+                                              const double *__restrict__ wbar = nullptr, double *__restrict__ pt = nullptr)
+{
+    double pv[NB], rv[NB];
+    ldb<NB>(p, pv);
+    ldb<NB>(r, rv);
+#pragma unroll
+    for (int b = 0; b < NB; ++b)
+        if (live[b]) pv[b] = rv[b] + beta[b] * pv[b];
+    stb<NB>(p, pv);
+    if (wbar) {
+        double a[NB];
+        ldb<NB>(wbar, a);
+#pragma unroll
+        for (int b = 0; b < NB; ++b) pv[b] *= a[b];
+        stb<NB>(pt, pv);
+    }
+}
+
 // Wave sums of V values per lane (V a power of two <= 64) by a reduce-scatter butterfly:
 // the first log2 V steps exchange half of the remaining values (each lane keeps the half
 // its lane bit selects), the rest reduce the single value left, so V sums cost V - 1 + 6 -
@@ -261,6 +333,24 @@ inline unsigned grid_for(int64_t n, int64_t cap = 4096) { return (unsigned)std::
     case 2: { constexpr int NB = 2; __VA_ARGS__; } break;       \
     default: { constexpr int NB = 4; __VA_ARGS__; } break;      \
     }
+
+// destriper_cg.hip's launchers as the ground solve (destriper_ground.hip) uses them: one band, on
+// the problem's CG stream, scalars (d->scal), stop flags (d->flags) and partials (d->part).
+//   ds_cg_state        the CG stream, event, stop flags and pinned read-back blocks (no vectors)
+//   ds_cg_use_graph    COMAP_DS_CGGRAPH / the size rule of the plain solve
+//   ds_launch_bin / ds_launch_project   the plain problem's bin and projection
+//   ds_dot             out = a . b over n values
+//   ds_dot_part        k_dot_part alone: kRedBlocks block partials of a . b in d->part
+//   ds_upd_grid        the CG update's grid (hence its r.r partials) for NO offsets
+int ds_cg_state(comap_destriper *d);
+bool ds_cg_use_graph(const comap_destriper *d);
+void ds_launch_bin(const comap_destriper *d, hipStream_t st, const double *x, const double *base, const double *hdiv,
+                   double *num, const int32_t *flags, bool hit_rows, bool x_scaled);
+void ds_launch_project(const comap_destriper *d, hipStream_t st, const double *x, const double *num, const double *h,
+                       double *y, const int32_t *flags);
+void ds_dot(comap_destriper *d, hipStream_t st, const double *a, const double *b, int64_t n, double *out);
+void ds_dot_part(comap_destriper *d, hipStream_t st, const double *a, const double *b, int64_t n);
+unsigned ds_upd_grid(int64_t NO);
 
 // a problem's persistent buffers come from the cached device pool (comap_tmp_alloc) in
 // the context stream's order; comap_destripe_destroy returns them after a device sync

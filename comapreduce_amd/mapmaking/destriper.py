@@ -135,7 +135,8 @@ def cg_solve(ops, allreduce, threshold=1e-6, niter=100, h=None, nnum=None):
         ops.cg_direction(rrn, rr, p, r)
         ops.set_scalar(rr, rrn)
         it = i + 1
-        delta = ops.host_scalar(rrn) / thresh0
+        with np.errstate(divide='ignore', invalid='ignore'):    # b = 0: NaN (0 / 0) stops, as on the device
+            delta = np.float64(ops.host_scalar(rrn)) / np.float64(thresh0)
         if np.isnan(delta) or delta < threshold:
             break
     return x, it, h, nnum
@@ -580,6 +581,9 @@ class GroundOps:
         self._folded = None                          # (vector, its version) xp was folded from by bin()
         self.mu, self.sigma = ops.zeros(self.K), ops.zeros(self.K)
         self._c('comap_destripe_ground_stats', self.g, N.dptr(self.mu), N.dptr(self.sigma))
+        # groups crossing azimuth 0 / 360 (raw span > 180 deg): their az < 180 entered as az + 360
+        self.wrapped = torch.zeros(self.K, dtype=torch.int32, device=self.dev)
+        self._c('comap_destripe_ground_wrapped', self.g, N.dptr(self.wrapped))
 
     def __del__(self):
         try:
@@ -680,12 +684,28 @@ class GroundOps:
         self._c('comap_destripe_ground_tail_direction', self.g, self.ops._s(rr_new), self.ops._s(rr), self._tail(p),
                 self._tail(r))
 
+    # ---- single-rank native solve (no Python per iteration)
+    def solve_native(self, threshold, niter):
+        """comap_destripe_ground_solve: (u [N/L + 2K] = x internal order | s | c, iterations,
+        maps {k: [npix]}): ``cg_solve`` on this operator and _solve_ground's maps, run on the
+        device as replayed graph batches with a device stop flag."""
+        self._folded = None
+        u = self.ops.empty(self.n_offsets)                    # the solve writes u and every map in full
+        maps = {k: self.ops.empty(self.npix) for k in ('map', 'naive', 'weight', 'hits')}
+        it = ctypes.c_int32()
+        self._c('comap_destripe_ground_solve', self.g, float(threshold), int(niter), N.dptr(u), N.dptr(maps['map']),
+                N.dptr(maps['naive']), N.dptr(maps['weight']), N.dptr(maps['hits']), ctypes.byref(it))
+        return u, int(it.value), maps
+
     # ---- results
     def fit(self, u):
         """(slope [K], level [K]) in the reference's units (per degree of raw azimuth):
         slope = s / sigma, level = c - s mu / sigma (slope 0 where sigma == 0).  The level is
         defined only up to the offsets' null space: a constant moved between c_k and the
-        group's offsets changes no residual, and CG from 0 returns the minimum-norm split."""
+        group's offsets changes no residual, and CG from 0 returns the minimum-norm split.
+        A group that crosses azimuth 0 / 360 (``self.wrapped``) was fitted on its unwrapped
+        series (az + 360 where az < 180): its mu may exceed 360 and its level is relative to
+        azimuth on [180, 540)."""
         _, s, c = self.split(u)
         torch = self.torch
         slope = torch.where(self.sigma > 0, s / torch.where(self.sigma > 0, self.sigma, torch.ones_like(self.sigma)),
@@ -1038,25 +1058,36 @@ class DeviceDestriper:
 
 
     def _solve_ground(self, threshold, niter, to_host):
-        """solve() with the ground template: the eager ``cg_solve`` on GroundOps, then the maps
-        from the offsets AND the fitted templates.  Adds 'ground': {'obsids', 'feeds', 'slope',
-        'level'} (host arrays [n_obs, n_feeds], GroundOps.fit's units); 'x' holds the offsets."""
+        """solve() with the ground template: the native device-resident CG on GroundOps
+        (``GroundOps.solve_native``; COMAP_DS_GROUND_SOLVE=eager, read here: the eager
+        ``cg_solve`` driver, the comparison baseline), then the maps from the offsets AND the
+        fitted templates.  Adds 'ground': {'obsids', 'feeds', 'slope', 'level', 'wrapped'} (host
+        arrays [n_obs, n_feeds], GroundOps.fit's units; 'wrapped': the group crosses azimuth
+        0 / 360 and was fitted on az + 360 where az < 180); 'x' holds the offsets."""
         ops, g = self.ops, self.gops
-        u, it, h, nnum = cg_solve(g, lambda t: t, threshold, niter)
-        _, hits, _ = ops.local_maps()
-        num = ops.zeros(ops.npix)
-        g.bin(u, 1, num)
-        maps = {'map': ops.zeros(ops.npix), 'naive': ops.zeros(ops.npix), 'weight': h, 'hits': hits}
-        ops.div_map(num, h, maps['map'])
-        ops.div_map(nnum, h, maps['naive'])
+        mode = os.environ.get('COMAP_DS_GROUND_SOLVE', 'native')
+        if mode == 'eager':
+            u, it, h, nnum = cg_solve(g, lambda t: t, threshold, niter)
+            _, hits, _ = ops.local_maps()
+            num = ops.zeros(ops.npix)
+            g.bin(u, 1, num)
+            maps = {'map': ops.zeros(ops.npix), 'naive': ops.zeros(ops.npix), 'weight': h, 'hits': hits}
+            ops.div_map(num, h, maps['map'])
+            ops.div_map(nnum, h, maps['naive'])
+        elif mode == 'native':
+            u, it, maps = g.solve_native(threshold, niter)
+        else:
+            raise ValueError(f"COMAP_DS_GROUND_SOLVE must be 'native' or 'eager', not {mode!r}")
         if self.layout is not None:
             maps = {k: self._untile(v, 1) for k, v in maps.items()}
         maps['map2'] = maps['weight']
         uobs, ufeed = self.ground
         slope, level = (v.cpu().numpy().reshape(uobs.size, ufeed.size) for v in g.fit(u))
+        wrapped = g.wrapped.cpu().numpy().reshape(uobs.size, ufeed.size) != 0
         # ('solution': the whole CG vector [x internal order | s | c], GroundOps' units)
         return {'x': ops.natural(u), 'iters': it, 'maps': maps_to_host(maps) if to_host else maps,
-                'ground': {'obsids': uobs, 'feeds': ufeed, 'slope': slope, 'level': level}, 'solution': u}
+                'ground': {'obsids': uobs, 'feeds': ufeed, 'slope': slope, 'level': level, 'wrapped': wrapped},
+                'solution': u}
 
 
 def maps_to_host(maps):

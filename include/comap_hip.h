@@ -385,8 +385,15 @@ int comap_destripe_ground_destroy(comap_ground *g);
 int64_t comap_destripe_ground_n_groups(const comap_ground *g);
 /* (group, pixel) entries: group-major (incl. off-map reads) and pixel-major (binned only) */
 int comap_destripe_ground_nnz(const comap_ground *g, int64_t *nnz_group_major, int64_t *nnz_pixel_major);
-/* mu_dev / sigma_dev f64 [K] (either may be NULL): each group's azimuth mean and rms */
+/* mu_dev / sigma_dev f64 [K] (either may be NULL): each group's azimuth mean and rms.
+ * Azimuth wrap: a group whose raw azimuths span more than 180 degrees (max - min > 180; no scan
+ * throws 180 degrees) crosses 0 / 360, and every azimuth v < 180 of such a group is used as
+ * v + 360.0 wherever the set-up reads it (one f64 add before any arithmetic), so mu and sigma are
+ * those of the unwrapped series (mu may exceed 360) and the level of such a group is relative to
+ * azimuth on [180, 540).  Groups that are not flagged keep the raw values. */
 int comap_destripe_ground_stats(comap_ground *g, double *mu_dev, double *sigma_dev);
+/* flag_dev int32 [K]: 1 where the group was unwrapped (above), else 0 */
+int comap_destripe_ground_wrapped(comap_ground *g, int32_t *flag_dev);
 /* xprime[i] = x[i] + c[g(i)] over the N/L offsets (internal order) */
 int comap_destripe_ground_fold(comap_ground *g, const double *x_dev, const double *c_dev, double *xprime_dev);
 /* num_p += sum over pixel row p of ga_e s_{k(e)}, ga_e = sum w a over group k's samples binned
@@ -414,6 +421,19 @@ int comap_destripe_ground_tail_update(comap_ground *g, const double *rr_dev, con
                                       double *r_dev, const double *p_dev, const double *q_dev, double *rr_new_dev);
 int comap_destripe_ground_tail_direction(comap_ground *g, const double *rr_new_dev, const double *rr_dev,
                                          double *p_dev, const double *r_dev);
+/* The whole ground solve on the device, the CG the calls above make under Python's cg_solve: u = 0,
+ * r = p = b (comap_destripe_project(NULL) then the _rhs tail), per iteration q = A p, alpha =
+ * rr / p.q, u += alpha p, r -= alpha q, p = r + (rr_new / rr) p; it stops after an iteration whose
+ * rr_new / rr0 is NaN or < threshold, or after niter iterations (*iters_out).  Iterations run on
+ * the problem's CG stream, 16 per replayed hipGraph batch with a device stop flag and one host
+ * check per batch (a remainder of fewer than 16 as plain launches; COMAP_DS_CGGRAPH as for
+ * comap_destripe_solve), 9 launches each; every sum is fixed-order and taken in the order of the
+ * per-piece calls above, so two solves agree bit for bit, with or without the graph, and with
+ * Python's cg_solve on those calls.  u_dev f64 [N/L + 2K]: x (internal offset order) | s | c.
+ * map = (naive numerator - W x' - ground bin(s)) / h, naive, weight, hits f64 [npix] (any may be
+ * NULL).  niter < 0 or a NULL g / u_dev: -1.  Synchronises. */
+int comap_destripe_ground_solve(comap_ground *g, double threshold, int32_t niter, double *u_dev, double *map_dev,
+                                double *naive_dev, double *weight_dev, double *hits_dev, int32_t *iters_out);
 
 /* ------------------------------------------------------------ destriper data prep (COMAPData.py) */
 /* One Level-2 file's inputs to comap_prep_gather (device pointers).  Output row r

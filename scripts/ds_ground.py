@@ -5,8 +5,9 @@
 C4 inputs: synthetic.level2_mapmaking observations (19 feeds, 45 000 samples) through
 COMAPData.read_comap_data (band 0, L = 50) onto the 480 x 480 CAR map, on the tiled layout.
 Per problem size, with early exit disabled (threshold 0) and a host clock around work that
-ends in a device synchronise, the three drivers alternated over ``rounds`` (median reported):
+ends in a device synchronise, the four drivers alternated over ``rounds`` (median reported):
 
+* ground_native -- comap_destripe_ground_solve (replayed graph batches), the ground default;
 * ground   -- cg_solve on GroundOps (offsets + slope and level per (observation, feed));
 * eager    -- cg_solve on the plain DeviceOps (the same Python driver, no ground terms);
 * native   -- comap_destripe_solve (replayed graph batches), the plain production path.
@@ -73,7 +74,8 @@ def measure(n_obs, niter, rounds, calls, device):
     dd = D.DeviceDestriper(pix, tod, w, 50, 480 * 480, device, map_shape=(480, 480), ground=(az, feedid, obsids))
     ops, g = dd.ops, dd.gops
     same = lambda t: t  # noqa: E731
-    drivers = {'ground': lambda: D.cg_solve(g, same, 0.0, niter)[1],
+    drivers = {'ground_native': lambda: g.solve_native(0.0, niter)[1],
+               'ground': lambda: D.cg_solve(g, same, 0.0, niter)[1],
                'eager': lambda: D.cg_solve(ops, same, 0.0, niter)[1],
                'native': lambda: ops.solve_native(0.0, niter)[1][0]}
     for fn in drivers.values():                 # warm every path (code objects, allocations, the graph)
@@ -101,6 +103,8 @@ def measure(n_obs, niter, rounds, calls, device):
     return {'observations': n_obs, 'n_samples': int(tod.size), 'n_offsets': ops.n_offsets, 'groups': g.K,
             'niter': niter, 'nnz_offset_pixel': ops.nnz(), 'nnz_ground': [nnz_g, nnz_b],
             'ms_per_iter': med, 'ms_per_iter_all': ms, 'ground_over_eager': med['ground'] / med['eager'],
+            'ground_native_over_ground': med['ground_native'] / med['ground'],
+            'ground_native_over_native': med['ground_native'] / med['native'],
             'ground_bin_ms': t_bin, 'ground_project_ms': t_proj,
             'ground_bin_GBps': nnz_b * 12 / t_bin / 1e6, 'ground_project_GBps': nnz_g * 12 / t_proj / 1e6,
             'both_GBps_on_2nnz12': 2 * nnz_g * 12 / (t_bin + t_proj) / 1e6}
