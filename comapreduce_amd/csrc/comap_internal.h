@@ -211,17 +211,23 @@ struct comap_l1_plan {
     // the other ranks' units): (feed, t0, n); comap_l1_average zeroes the outputs there
     int64_t *gaps = nullptr;           // dev [NG][3]
     int64_t n_gaps = 0, max_gap = 0;
-    // pass B -> median -> pass C software pipeline over unit groups (comap_l1_average):
-    // group g = units [grp_u0[g], grp_u0[g+1]) = tiles [grp_tile0[g], grp_tile0[g+1]);
-    // its sliding medians (one job per (unit, band)) run on the side stream
-    static constexpr int kMaxGroups = 4;
+    // pass B -> median -> tail pipeline over unit groups (comap_l1_average): group g =
+    // units [grp_u0[g], grp_u0[g+1]) = tiles [grp_tile0[g], grp_tile0[g+1]) = pass-B tiles
+    // [grpb_tile0[g], grpb_tile0[g+1]).  Everything after pass B is per unit, so a group's
+    // whole chain (B, median, series sums, pass C, phase 1, finish, scan weights) depends on
+    // no other group.  Default schedule (chain): pass B stays on the main stream and the
+    // medians run on `side` (ev_b / ev_m); pipe_alt: whole chains alternate between the main
+    // stream and `side`.
+    static constexpr int kMaxGroups = 16;
     int32_t ngroups = 0;
+    bool pipe_alt = false;             // COMAP_L1_PIPE=chain (default) | alt
     int32_t grp_u0[kMaxGroups + 1] = {0};
     int64_t grp_tile0[kMaxGroups + 1] = {0};
     int64_t grpb_tile0[kMaxGroups + 1] = {0};
     MedPlan medg[kMaxGroups];
     hipStream_t side = nullptr;
     hipEvent_t ev_b[kMaxGroups] = {}, ev_m[kMaxGroups] = {};
+    hipEvent_t ev_pre = nullptr, ev_join = nullptr;   // alt: phase 0 done (main), last side kernel done
     // device workspaces
     double *airmass = nullptr;         // [F][T]
     double *unit_sums = nullptr;       // [U][8]: n, SA, SAA, Sv, Svv, N4
@@ -279,7 +285,7 @@ struct comap_l1_plan {
     double *ubs = nullptr;             // [U*4][4] fit normal-equation sums n, SA, SAA per (unit, band)
     double *fitsum = nullptr;          // [2][U*4096] masked Sd, SAd (select_time path)
     double *oa = nullptr;              // [U*4096][2] offset/slope L1AGC subtracts
-    int32_t *flag = nullptr;           // [1] phase-1 kappa mismatch -> legacy passes C, D run
+    int32_t *flag = nullptr;           // [kMaxGroups] phase-1 kappa mismatch in group g -> its legacy pass D runs
     // non-finite filtered rows (k_unit_flags, k_special_rows): ynf[u] = the gain fit's input
     // holds a non-finite value (dG = 0); ugate[u] = a band-0 row's filtered values hold
     // +-inf (fit_power_spectrum raises: dG None, no in-place zeroing)

@@ -42,9 +42,17 @@
 
 using namespace comap;
 
+// Unit groups of comap_l1_average's pipeline: pass B, the median and the whole tail run per
+// group of units, each group's median on a side stream under the next group's pass B.
+// 0: the count follows the plan's size -- the fewest groups whose pass B fits the blocks
+// the chip holds at once, or one group when that gives fewer than kGroupsAutoMin (C2: 8,
+// a C3 shard of 8 and the small observations: 1; comap_l1_plan_create has the rule,
+// DESIGN §3.1 the sweep).  A positive value fixes the count.  The COMAP_GROUPS environment
+// variable, read when a plan is created, overrides either.
 #ifndef COMAP_GROUPS
-#define COMAP_GROUPS 1      // unit groups of the pass B / median / pass C pipeline (2 measured no faster with the sort-path median)
+#define COMAP_GROUPS 0
 #endif
+constexpr int kGroupsAutoMin = 3;
 
 typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
 // Streaming load of 4 cube samples, non-temporal: data read once never allocates in
@@ -491,7 +499,7 @@ __global__ void k_atmos_fit(const int32_t *__restrict__ units, const double *__r
 // channels; per (unit, band): beta = sum alpha o, gamma = sum alpha a, N.
 // Also gathers the (unit, channel) offsets / slopes L1AGC subtracts (k_gather_oa's job:
 // the unit's scan fit, or (nanmedian, 0) for calibrators) into oa for k_coef_d, and
-// block 0 clears the pass-D mismatch flag -- two launches fewer per step.
+// block 0 clears the pass-D mismatch flags (one per unit group) -- two launches fewer per step.
 __global__ void __launch_bounds__(256) k_coef_b(const int32_t *__restrict__ units, const double *__restrict__ us,
                                                 const double *__restrict__ mom, int64_t UC,
                                                 const double *__restrict__ fit, int F, const float *__restrict__ med,
@@ -503,7 +511,7 @@ __global__ void __launch_bounds__(256) k_coef_b(const int32_t *__restrict__ unit
     const int ub = blockIdx.x;
     const int u = ub / kBands, b = ub % kBands;
     const int n = units[4 * u + 3];
-    if (ub == 0 && threadIdx.x == 0) *flag = 0;
+    if (ub == 0 && threadIdx.x < comap_l1_plan::kMaxGroups) flag[threadIdx.x] = 0;   // one flag per unit group
     const int fu = units[4 * u], su = units[4 * u + 1];
     const double *fo = fit + (((int64_t)su * F + fu) * kBands + b) * 2 * kChannels;
     const double *q = us + 8 * (int64_t)u;
@@ -1015,7 +1023,9 @@ __device__ __forceinline__ void special_weights(int c, double tsv, double nf, do
 //   Korig the same weights * Tsys                          (tod_original)
 // Level1Averaging.py:701-705, 710-725, 841-867; GainSubtraction.py:190-201.
 // dsum[ub][..] = {Sg_b, Gg_b, Dg_b, Sr_b, Gr_b, Dr_b, So_b, Go_b, Do_b, SKr, SW, SWo}
-__global__ void __launch_bounds__(256) k_coef_d(const int32_t *__restrict__ units, const double *__restrict__ us,
+// Block k serves pair ub0 + k (a unit group's range; phase 0 runs over every pair); flag is
+// the group's mismatch flag.
+__global__ void __launch_bounds__(256) k_coef_d(int ub0, const int32_t *__restrict__ units, const double *__restrict__ us,
                                                 const double *__restrict__ mom, int64_t UC,
                                                 const double *__restrict__ oa,
                                                 const double *__restrict__ alpha, const double *__restrict__ nf,
@@ -1035,7 +1045,7 @@ __global__ void __launch_bounds__(256) k_coef_d(const int32_t *__restrict__ unit
 {
     __shared__ double red[4];
     __shared__ double s_kap[4][kChannels];     // alpha, kg, kr, ko (phase 0 channel list)
-    const int ub = blockIdx.x;
+    const int ub = ub0 + blockIdx.x;
     const int u = ub / kBands, b = ub % kBands;
     const int f = units[4 * u];
     const double *q = us + 8 * (int64_t)u;
@@ -1301,9 +1311,10 @@ __global__ void __launch_bounds__(256) k_special_rows(int mode, const int32_t *_
 // kappa_r, kappa_o; dG_t = sum over the 4 bands; then
 //   tod_b  = (Sr_b - dG SKr_b) / SW_b           (residual band average)
 //   orig_b = So_b / SWo_b                        (tod_original)
+// Block k serves tile tile0 + k (a unit group's tile range); flag is that group's.
 __global__ void __launch_bounds__(256) k_gain_avg(const float *__restrict__ tod, const double *__restrict__ A,
                                                   const int32_t *__restrict__ units, const int32_t *__restrict__ tiles,
-                                                  int64_t T, int64_t UC, const double *__restrict__ kap,
+                                                  int64_t tile0, int64_t T, int64_t UC, const double *__restrict__ kap,
                                                   const double *__restrict__ dsum, const double *__restrict__ mf,
                                                   double *__restrict__ tod_out, double *__restrict__ orig_out,
                                                   double *__restrict__ dG_out, const int32_t *__restrict__ flag)
@@ -1312,7 +1323,8 @@ __global__ void __launch_bounds__(256) k_gain_avg(const float *__restrict__ tod,
     if (*flag == 0) return;                         // legacy pass D: only after a fused-path mismatch
     const int b = uniform(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
-    const int u = tiles[2 * blockIdx.x], toff = tiles[2 * blockIdx.x + 1];
+    const int64_t tile = tile0 + blockIdx.x;
+    const int u = tiles[2 * tile], toff = tiles[2 * tile + 1];
     const int f = units[4 * u], t0 = units[4 * u + 2], n = units[4 * u + 3];
     const int r0 = toff + 4 * lane;
     const float *base = tod + (int64_t)(f * kBands + b) * kChannels * T + t0 + r0;
@@ -1396,11 +1408,11 @@ __device__ __forceinline__ void scan_weight_band(const double *__restrict__ r, i
     for (int t = threadIdx.x; t < n; t += blockDim.x) wo[t] = wt;
 }
 
-__global__ void __launch_bounds__(256) k_scan_weights(const int32_t *__restrict__ units, int64_t T,
+__global__ void __launch_bounds__(256) k_scan_weights(int ub0, const int32_t *__restrict__ units, int64_t T,
                                                       const double *__restrict__ tod_out, double *__restrict__ w_out)
 {
     __shared__ double red[4];
-    const int ub = blockIdx.x;
+    const int ub = ub0 + blockIdx.x;
     const int u = ub / kBands, b = ub % kBands;
     const int f = units[4 * u], t0 = units[4 * u + 2], n = units[4 * u + 3];
     const int64_t o = (int64_t)(f * kBands + b) * T + t0;
@@ -1415,17 +1427,18 @@ __global__ void __launch_bounds__(256) k_scan_weights(const int32_t *__restrict_
 // cost far more than the launch: the pass-D body's registers and 32 KB of LDS ride on
 // every finish block, 103 -> 1448 us at C2, r03s2; reverted.)
 __global__ void __launch_bounds__(256) k_finish(const int32_t *__restrict__ units, const int32_t *__restrict__ tiles,
-                                                int64_t T, const double *__restrict__ A,
+                                                int64_t tile0, int64_t T, const double *__restrict__ A,
                                                 const double *__restrict__ mf, const double *__restrict__ dsum,
                                                 double *__restrict__ tod_out, double *__restrict__ orig_out,
                                                 double *__restrict__ dG, const int32_t *__restrict__ flag)
 {
     if (*flag != 0) return;                          // mismatch: the legacy passes produce the outputs
-    const int u = tiles[2 * blockIdx.x];
+    const int64_t tile = tile0 + blockIdx.x;         // a unit group's tile range
+    const int u = tiles[2 * tile];
     const int f = units[4 * u], t0 = units[4 * u + 2], n = units[4 * u + 3];
     const double *ds = dsum + 16 * (int64_t)u * kBands;
     for (int k = threadIdx.x; k < kTile; k += 256) {
-        const int r = tiles[2 * blockIdx.x + 1] + k;
+        const int r = tiles[2 * tile + 1] + k;
         if (r >= n) break;
         const int64_t t = t0 + r;
         const double a = A[(int64_t)f * T + t];
@@ -1729,7 +1742,7 @@ extern "C" int comap_l1_plan_create(comap_ctx *ctx, const comap_obs_desc *d, com
     const int64_t UC = (int64_t)p->U * kBC;
     int rc = 0;
     if (p->n_gaps) rc |= upload(ctx, (void **)&p->gaps, gaps.data(), gaps.size() * 8);
-    rc |= dalloc(ctx, &p->flag, 1);
+    rc |= dalloc(ctx, &p->flag, comap_l1_plan::kMaxGroups);
     rc |= dalloc(ctx, &p->dlist, (size_t)p->U * kBC);
     rc |= dalloc(ctx, &p->dcnt, (size_t)p->U * kBands);
     rc |= dalloc(ctx, &p->dw, 4 * (size_t)p->U * kBC);
@@ -1772,11 +1785,33 @@ extern "C" int comap_l1_plan_create(comap_ctx *ctx, const comap_obs_desc *d, com
         if (!strcmp(r, "legacy")) p->regress_legacy = true;
         else if (strcmp(r, "fused")) { comap_l1_plan_destroy(p); return comap_fail(ctx, -1, "COMAP_L1_REGRESS must be fused or legacy"); }
     }
-    // pass B / median / pass C pipeline groups (comap_l1_average): contiguous unit ranges
-    // COMAP_GROUPS (env) overrides the compiled default -- measurement knob
+    // unit groups of comap_l1_average's pipeline: contiguous unit ranges.  Consecutive pass-B
+    // launches do not overlap, so each one ends with the chip draining: a launch of b blocks
+    // on a chip that holds R of them costs ceil(b / R) block lifetimes whatever b is (C2:
+    // R = 512, 1.25 ms; measured, DESIGN §3.1: 6 groups of 567 blocks cost pass B 2.5 ms more
+    // than one launch, 8 groups of 425 cost 0.1-0.4).  The count is therefore the smallest
+    // that keeps a group's pass B inside one set of resident blocks, filled to 7/8 at most
+    // (the groups are unit ranges, not equal block counts).  One group stays when that
+    // count is below kGroupsAutoMin (two groups measured no faster than one at a quarter of
+    // C2) or would fill the chip to less than 0.7 on average (each launch still costs a whole
+    // block lifetime): a C3 shard of 8 and the small observations keep one group.
+    // COMAP_GROUPS (env) overrides the count -- measurement knob
     int groups = COMAP_GROUPS;
+    if (groups <= 0) {
+        int per_cu = 0, cus = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_band_sums, 256, 0) != hipSuccess) per_cu = 0;
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess) cus = 0;
+        const int64_t resident = (int64_t)per_cu * cus, fill = resident * 7 / 8, blocks = (int64_t)kSubB * tub[p->U];
+        groups = fill > 0 ? (int)std::min<int64_t>(comap_l1_plan::kMaxGroups, (blocks + fill - 1) / fill) : 1;
+        if (groups < kGroupsAutoMin || blocks * 10 < groups * resident * 7) groups = 1;
+    }
     if (const char *g = getenv("COMAP_GROUPS")) groups = atoi(g);
     p->ngroups = std::max(1, std::min(std::min(groups, comap_l1_plan::kMaxGroups), (int)p->U));
+    // COMAP_L1_PIPE=chain (default) | alt: how the groups are scheduled (comap_l1_average)
+    if (const char *r = getenv("COMAP_L1_PIPE")) {
+        if (!strcmp(r, "alt")) p->pipe_alt = true;
+        else if (strcmp(r, "chain")) { comap_l1_plan_destroy(p); return comap_fail(ctx, -1, "COMAP_L1_PIPE must be chain or alt"); }
+    }
     {
         std::vector<int64_t> tu(p->U + 1, 0);
         for (int u = 0; u < p->U; ++u) tu[u + 1] = tu[u] + (p->units_h[4 * u + 3] + kTile - 1) / kTile;
@@ -1786,9 +1821,9 @@ extern "C" int comap_l1_plan_create(comap_ctx *ctx, const comap_obs_desc *d, com
             p->grpb_tile0[g] = tub[p->grp_u0[g]];
         }
     }
-    // the median side stream may run at a higher priority than the streaming passes
-    // (COMAP_SIDE_PRIO=1): its latency-bound kernels then take CU slots first while
-    // the next group's bandwidth-bound pass B runs on the rest
+    // the side stream may run at a higher priority than the main stream (COMAP_SIDE_PRIO=1):
+    // its latency-bound kernels then take CU slots first while the next group's
+    // bandwidth-bound pass B runs on the rest (measured: no difference, DESIGN Appendix A)
     int prio = 0;
     if (const char *sp = getenv("COMAP_SIDE_PRIO"); sp && sp[0] == '1') {
         int lo = 0, hi = 0;
@@ -1798,6 +1833,8 @@ extern "C" int comap_l1_plan_create(comap_ctx *ctx, const comap_obs_desc *d, com
     for (int g = 0; g < p->ngroups && ok; ++g)
         ok = hipEventCreateWithFlags(&p->ev_b[g], hipEventDisableTiming) == hipSuccess &&
              hipEventCreateWithFlags(&p->ev_m[g], hipEventDisableTiming) == hipSuccess;
+    ok = ok && hipEventCreateWithFlags(&p->ev_pre, hipEventDisableTiming) == hipSuccess &&
+         hipEventCreateWithFlags(&p->ev_join, hipEventDisableTiming) == hipSuccess;
     if (!ok) { comap_l1_plan_destroy(p); return comap_fail(ctx, -2, "side stream / events"); }
     // median jobs per group: (unit, band) series, reflect-3 padded [rev, x, rev], outputs [n, 2n)
     // (bands of scans shorter than 2w are skipped by median_filter: no outputs)
@@ -1849,6 +1886,8 @@ extern "C" int comap_l1_plan_destroy(comap_l1_plan *p)
         if (p->ev_b[g]) (void)hipEventDestroy(p->ev_b[g]);
         if (p->ev_m[g]) (void)hipEventDestroy(p->ev_m[g]);
     }
+    if (p->ev_pre) (void)hipEventDestroy(p->ev_pre);
+    if (p->ev_join) (void)hipEventDestroy(p->ev_join);
     if (p->side) (void)hipStreamDestroy(p->side);
     if (p->nan_host) (void)hipHostFree(p->nan_host);
     if (p->mom_event) (void)hipEventDestroy(p->mom_event);
@@ -2117,10 +2156,11 @@ extern "C" int comap_l1_average(comap_l1_plan *p, const double *fit, const doubl
     const bool special = p->nan_total > 0;
     // the special-row path needs every channel's x (xreg): all pairs take pass C, as does legacy mode
     const int force_c = (special || p->regress_legacy) ? 1 : 0;
-    auto coef_d = [&](int phase, const int32_t *ugate) {
-        k_coef_d<<<UB, 256, 0, st>>>(p->units, p->unit_sums, p->mom, UC, p->oa, p->alpha, p->nf, p->bsum, p->ssum,
+    // k_coef_d over the pairs [ub0, ub0 + nub) on stream s; flag: the mismatch flag phase 1 sets
+    auto coef_d = [&](int phase, int ub0, int nub, int32_t *flag, const int32_t *ugate, hipStream_t s) {
+        k_coef_d<<<nub, 256, 0, s>>>(ub0, p->units, p->unit_sums, p->mom, UC, p->oa, p->alpha, p->nf, p->bsum, p->ssum,
                                      p->sdm, tsys0, gain0, p->gw, p->gmode, calibrator, p->kap, p->dsum, p->xreg,
-                                     phase, p->flag, p->dlist, p->dcnt, p->dw, p->rowbad, p->tod, p->T, p->airmass,
+                                     phase, flag, p->dlist, p->dcnt, p->dw, p->rowbad, p->tod, p->T, p->airmass,
                                      p->mf, p->ynf, ugate, p->pdot, p->pgate, p->needc);
     };
     auto special_rows = [&](int mode) {
@@ -2129,76 +2169,165 @@ extern "C" int comap_l1_average(comap_l1_plan *p, const double *fit, const doubl
                                            tod_out, orig_out);
     };
     // phase 0: the kappa weights and the channel list (no regression needed)
-    PROF(p, KV_COEF_D, coef_d(0, nullptr));
+    PROF(p, KV_COEF_D, coef_d(0, 0, UB, p->flag, nullptr, st));
     COMAP_LAUNCH_CHECK(ctx);
-    // Pass B (band means + every per-sample output sum), the sliding median with the series
-    // sums and dots that stand in for pass C, and pass C itself (regression sums, only for
-    // the pairs k_series_sums gated out: needc) are software-pipelined over the unit groups:
-    //   main: B0 B1 .. | wait M0: C0 | wait M1: C1 ..     side: wait B0: M0 | wait B1: M1 ..
-    // so each group's median (latency-bound) runs under the next group's streaming pass;
-    // the main stream has waited for every group's median before phase 1.
+    // The rest is per unit group g (contiguous units, their tiles and (unit, band) pairs),
+    // each step on the stream the schedule below gives it:
+    //   B_g     pass B: band means + every per-sample output sum
+    //   M_g     the sliding median, then the series sums and dots that stand in for pass C
+    //   C_g     pass C (regression sums, only for the pairs k_series_sums gated out: needc)
+    //   T_g     phase 1 (per-band constants), the legacy pass D behind the group's flag,
+    //           k_finish and the scan weights
+    const int G = p->ngroups;
+    auto band_sums = [&](int g, hipStream_t s) -> int {
+        const int64_t t0 = p->grpb_tile0[g], nt = p->grpb_tile0[g + 1] - t0;
+        PROF_ON(p, KV_BAND_SUMS, s, k_band_sums<<<kSubB * nt, 256, 0, s>>>(p->tod, p->airmass, p->units, p->tiles_b, t0,
+                                                                          p->T, p->dlist, p->dcnt, p->dw, p->bsum,
+                                                                          p->mb, tod_out, orig_out, p->dG, p->sgb));
+        COMAP_LAUNCH_CHECK(ctx);
+        return 0;
+    };
+    auto median_sums = [&](int g, hipStream_t s) -> int {
+        const int ub0 = p->grp_u0[g] * kBands, nub = (p->grp_u0[g + 1] - p->grp_u0[g]) * kBands;
+        int r = 0;
+        PROF_ON(p, KV_MEDIAN, s, r = comap_median_run(ctx, &p->medg[g], s));
+        if (r) return r;
+        PROF_ON(p, KV_SERIES_SUMS, s, k_series_sums<<<nub, 256, 0, s>>>(ub0, p->units, p->airmass, p->T, p->bsum, p->mf,
+                                                                       p->ssum, p->sgb, tod_out, orig_out, p->pgate,
+                                                                       force_c, p->pdot, p->needc));
+        COMAP_LAUNCH_CHECK(ctx);
+        return 0;
+    };
+    // pass C and the tail take a range of groups [g0, g1) (contiguous units)
+    auto regress = [&](int g0, int g1, hipStream_t s) -> int {
+        const int ub0 = p->grp_u0[g0] * kBands, nub = (p->grp_u0[g1] - p->grp_u0[g0]) * kBands;
+        PROF_ON(p, KV_REGRESS, s, k_regress<<<nub * kRegBlocks, 256, 0, s>>>(ub0, p->tod, p->mf, p->units, p->T, p->bsum,
+                                                                            p->dlist, p->dcnt, p->needc, p->sdm));
+        COMAP_LAUNCH_CHECK(ctx);
+        return 0;
+    };
+    // The tail of groups [g0, g1) alone.  Sound per range because everything it reads or
+    // writes is per unit and a group is a unit range: phase 1's constants, kappa and x belong
+    // to one (unit, band); dG and the outputs to one unit's samples; the scan weight to one
+    // (unit, band).  The mismatch flag is per group for the same reason: phase 1 of a range
+    // sets flag g0 when a kappa of one of ITS pairs depends on the regression, and only that
+    // range's tiles then take the legacy pass D instead of k_finish (k_coef_b cleared every
+    // flag before the first pass B).
+    // legacy pass D (k_gain_avg): exits at once unless phase 1 found a kappa that depends on
+    // the regression (a NaN regression coefficient), in which case it recomputes the outputs
+    // exactly from phase 1's constants (a former separate phase-2 k_coef_d launch
+    // recomputed what phase 1 had already written: dropped)
+    auto tail = [&](int g0, int g1, hipStream_t s) -> int {
+        const int ub0 = p->grp_u0[g0] * kBands, nub = (p->grp_u0[g1] - p->grp_u0[g0]) * kBands;
+        const int64_t t0 = p->grp_tile0[g0], nt = p->grp_tile0[g1] - t0;
+        int32_t *flag = p->flag + g0;
+        // phase 1: per-band constants -- from pass B's sums, or for needc pairs from the
+        // per-channel regression solve with the kappa re-check
+        PROF_ON(p, KV_COEF_D, s, coef_d(1, ub0, nub, flag, nullptr, s));
+        COMAP_LAUNCH_CHECK(ctx);
+        PROF_ON(p, KV_GAIN_AVG, s, k_gain_avg<<<nt, 256, 0, s>>>(p->tod, p->airmass, p->units, p->tiles, t0, p->T, UC,
+                                                                p->kap, p->dsum, p->mf, tod_out, orig_out, p->dG, flag));
+        COMAP_LAUNCH_CHECK(ctx);
+        PROF_ON(p, KV_FINISH, s, k_finish<<<nt, 256, 0, s>>>(p->units, p->tiles, t0, p->T, p->airmass, p->mf, p->dsum,
+                                                            tod_out, orig_out, p->dG, flag));
+        COMAP_LAUNCH_CHECK(ctx);
+        PROF_ON(p, KV_SCAN_WEIGHTS, s, k_scan_weights<<<nub, 256, 0, s>>>(ub0, p->units, p->T, tod_out, w_out));
+        COMAP_LAUNCH_CHECK(ctx);
+        return 0;
+    };
+    // work queued on the side stream is waited for on every return path (the outputs and
+    // this call's temporaries are consumed on the main stream)
+    struct SideJoin {
+        hipStream_t s;
+        bool armed = false;
+        ~SideJoin() { if (armed) (void)hipStreamSynchronize(s); }
+    } side_join{p->side};
+    if (G > 1 && p->pipe_alt && !special) {
+        // alt (COMAP_L1_PIPE=alt, kept for measurement): group g's whole chain B_g M_g C_g T_g
+        // on ONE stream (no event hop inside a chain), consecutive groups on alternating streams:
+        //   main: B0 M0 C0 T0 ...... B2 M2 C2 T2 ...
+        //   side:    [B0 done] B1 M1 C1 T1 ...... B3 M3 C3 T3
+        // A group's latency-bound tail runs under the other stream's pass B, and B_{g+1}'s
+        // blocks can take the CUs B_g's last blocks free.  The chains are staggered once
+        // (chain 1 waits for B_0): in lock-step two B's would share HBM and then two tails
+        // would share nothing.  Measured slower than chain at every count: two
+        // pass B's sharing the chip and small kernels waiting for slots under them cost more
+        // than the boundaries they avoid.  Ordering is by stream order and events only.
+        COMAP_CHECK(ctx, hipEventRecord(p->ev_pre, st));
+        COMAP_CHECK(ctx, hipStreamWaitEvent(p->side, p->ev_pre, 0));
+        side_join.armed = true;
+        for (int g = 0; g < G; ++g) {
+            hipStream_t s = (g & 1) ? p->side : st;
+            if (g == 1) COMAP_CHECK(ctx, hipStreamWaitEvent(s, p->ev_b[0], 0));
+            if ((rc = band_sums(g, s))) return rc;
+            if (g == 0) COMAP_CHECK(ctx, hipEventRecord(p->ev_b[0], s));
+            if ((rc = median_sums(g, s))) return rc;
+            if ((rc = regress(g, g + 1, s))) return rc;
+            if ((rc = tail(g, g + 1, s))) return rc;
+        }
+        COMAP_CHECK(ctx, hipEventRecord(p->ev_join, p->side));
+        COMAP_CHECK(ctx, hipStreamWaitEvent(st, p->ev_join, 0));
+        side_join.armed = false;
+        return 0;
+    }
+    // chain (the default; the special-row path at any setting): pass B stays on the main
+    // stream and each group's median runs on the side stream under the next group's B.  The
+    // main stream is busy with pass B until the last one ends, so the tail runs twice only:
+    // once for every group but the last (beside the last median), once for the last group:
+    //   main: B0 B1 .. B(G-1) | wait M0..M(G-2): C T of groups 0..G-2 | wait M(G-1): C T of G-1
+    //   side: wait B0: M0 | wait B1: M1 | ..                           | wait B(G-1): M(G-1)
+    // (a tail per group there is 5 launches each for nothing: 0.71 ms of tail kernels at 8
+    // groups against 0.38 with two tails).  Consecutive pass-B launches do not overlap;
+    // the group count keeps each inside one set of resident blocks (comap_l1_plan_create).
     // one group: the median stays on the main stream -- the two cross-stream event hops
     // cost ~20 us each at the C3 shard (r03s2 trace) and there is nothing to overlap
-    hipStream_t side = p->ngroups > 1 ? p->side : st;
-    for (int g = 0; g < p->ngroups; ++g) {
-        const int64_t t0 = p->grpb_tile0[g], nt = p->grpb_tile0[g + 1] - t0;
-        const int ub0 = p->grp_u0[g] * kBands, nub = (p->grp_u0[g + 1] - p->grp_u0[g]) * kBands;
-            PROF(p, KV_BAND_SUMS, k_band_sums<<<kSubB * nt, 256, 0, st>>>(p->tod, p->airmass, p->units, p->tiles_b, t0,
-                                                                        p->T, p->dlist, p->dcnt, p->dw, p->bsum,
-                                                                        p->mb, tod_out, orig_out, p->dG, p->sgb));
-        COMAP_LAUNCH_CHECK(ctx);
+    hipStream_t side = G > 1 ? p->side : st;
+    for (int g = 0; g < G; ++g) {
+        if ((rc = band_sums(g, st))) return rc;
         if (side != st) {
             COMAP_CHECK(ctx, hipEventRecord(p->ev_b[g], st));
             COMAP_CHECK(ctx, hipStreamWaitEvent(side, p->ev_b[g], 0));
+            side_join.armed = true;
         }
-        PROF_ON(p, KV_MEDIAN, side, rc = comap_median_run(ctx, &p->medg[g], side));
-        if (rc) return rc;
-        PROF_ON(p, KV_SERIES_SUMS, side, k_series_sums<<<nub, 256, 0, side>>>(ub0, p->units, p->airmass, p->T,
-                                                                             p->bsum, p->mf, p->ssum, p->sgb, tod_out,
-                                                                             orig_out, p->pgate, force_c, p->pdot,
-                                                                             p->needc));
-        COMAP_LAUNCH_CHECK(ctx);
+        if ((rc = median_sums(g, side))) return rc;
         if (side != st) COMAP_CHECK(ctx, hipEventRecord(p->ev_m[g], side));
     }
-    for (int g = 0; g < p->ngroups; ++g) {
-        const int ub0 = p->grp_u0[g] * kBands, nub = (p->grp_u0[g + 1] - p->grp_u0[g]) * kBands;
+    const int gs = (G > 1 && !special) ? G - 1 : G;      // the first tail: groups [0, gs)
+    for (int g = 0; g < gs; ++g)
         if (side != st) COMAP_CHECK(ctx, hipStreamWaitEvent(st, p->ev_m[g], 0));
-        PROF(p, KV_REGRESS, k_regress<<<nub * kRegBlocks, 256, 0, st>>>(ub0, p->tod, p->mf, p->units, p->T, p->bsum,
-                                                                       p->dlist, p->dcnt, p->needc, p->sdm));
-        COMAP_LAUNCH_CHECK(ctx);
+    if ((rc = regress(0, gs, st))) return rc;
+    if (!special && (rc = tail(0, gs, st))) return rc;
+    if (gs < G) {
+        COMAP_CHECK(ctx, hipStreamWaitEvent(st, p->ev_m[G - 1], 0));
+        if ((rc = regress(G - 1, G, st))) return rc;
+        if ((rc = tail(G - 1, G, st))) return rc;
     }
-    // phase 1: per-band constants -- from pass B's sums, or for needc pairs from the
-    // per-channel regression solve with the kappa re-check
-    PROF(p, KV_COEF_D, coef_d(1, nullptr));
+    side_join.armed = false;       // the main stream has waited for every group's last side kernel
+    if (!special) return 0;
+    // special rows: the tail once over every unit, in the order it has always had (the gate
+    // and the forced pass D couple it to k_special_rows); flag 0 serves every tile
+    PROF(p, KV_COEF_D, coef_d(1, 0, UB, p->flag, nullptr, st));
     COMAP_LAUNCH_CHECK(ctx);
-    if (special) {
-        // the fit_power_spectrum gate of units whose band-0 special rows hold +-inf, then the
-        // coefficients again with it (a kappa that changes sets the flag: legacy pass D)
-        COMAP_CHECK(ctx, hipMemsetAsync(p->ugate, 0, 4 * (size_t)p->U, st));
-        special_rows(0);
-        COMAP_LAUNCH_CHECK(ctx);
-        coef_d(2, p->ugate);
-        COMAP_LAUNCH_CHECK(ctx);
-        // pass B's fused sums took kappa 0 * inf = NaN at a special row's +-inf samples; the
-        // legacy pass D re-forms every output and skips kappa-0 channels
-        COMAP_CHECK(ctx, hipMemsetAsync(p->flag, 0xff, 4, st));
-    }
-    // legacy pass D: exits at once unless phase 1 found a kappa that depends on the
-    // regression (a NaN regression coefficient), in which case it recomputes the outputs
-    // exactly from phase 1's constants (a former separate phase-2 k_coef_d launch
-    // recomputed what phase 1 had already written: dropped)
-    PROF(p, KV_GAIN_AVG, k_gain_avg<<<p->n_tiles, 256, 0, st>>>(p->tod, p->airmass, p->units, p->tiles, p->T, UC,
+    // the fit_power_spectrum gate of units whose band-0 special rows hold +-inf, then the
+    // coefficients again with it (a kappa that changes sets the flag: legacy pass D)
+    COMAP_CHECK(ctx, hipMemsetAsync(p->ugate, 0, 4 * (size_t)p->U, st));
+    special_rows(0);
+    COMAP_LAUNCH_CHECK(ctx);
+    coef_d(2, 0, UB, p->flag, p->ugate, st);
+    COMAP_LAUNCH_CHECK(ctx);
+    // pass B's fused sums took kappa 0 * inf = NaN at a special row's +-inf samples; the
+    // legacy pass D re-forms every output and skips kappa-0 channels
+    COMAP_CHECK(ctx, hipMemsetAsync(p->flag, 0xff, 4, st));
+    PROF(p, KV_GAIN_AVG, k_gain_avg<<<p->n_tiles, 256, 0, st>>>(p->tod, p->airmass, p->units, p->tiles, 0, p->T, UC,
                                                                 p->kap, p->dsum, p->mf, tod_out, orig_out, p->dG,
                                                                 p->flag));
     COMAP_LAUNCH_CHECK(ctx);
-    PROF(p, KV_FINISH, k_finish<<<p->n_tiles, 256, 0, st>>>(p->units, p->tiles, p->T, p->airmass, p->mf, p->dsum,
+    PROF(p, KV_FINISH, k_finish<<<p->n_tiles, 256, 0, st>>>(p->units, p->tiles, 0, p->T, p->airmass, p->mf, p->dsum,
                                                             tod_out, orig_out, p->dG, p->flag));
     COMAP_LAUNCH_CHECK(ctx);
-    if (special) {
-        special_rows(1);
-        COMAP_LAUNCH_CHECK(ctx);
-    }
-    PROF(p, KV_SCAN_WEIGHTS, k_scan_weights<<<UB, 256, 0, st>>>(p->units, p->T, tod_out, w_out));
+    special_rows(1);
+    COMAP_LAUNCH_CHECK(ctx);
+    PROF(p, KV_SCAN_WEIGHTS, k_scan_weights<<<UB, 256, 0, st>>>(0, p->units, p->T, tod_out, w_out));
     COMAP_LAUNCH_CHECK(ctx);
     return 0;
 }
