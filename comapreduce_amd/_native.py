@@ -114,6 +114,12 @@ _SIGS = {
     'comap_destripe_ground_wrapped': (c_int, [c_void_p, c_void_p]),
     'comap_destripe_ground_solve': (c_int, [c_void_p, c_double, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                             c_void_p, P_int32]),
+    'comap_destripe_ground_dist_bin': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    'comap_destripe_ground_dist_project': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                   c_void_p]),
+    'comap_destripe_ground_dist_update': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                  c_void_p]),
+    'comap_destripe_ground_dist_direction': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'comap_prep_auto_rms': (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int64, c_void_p]),
     'comap_prep_percentiles': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_int64,
                                        c_void_p]),

@@ -73,6 +73,8 @@ struct comap_ground {
     // stream, scalars, stop flags and r.r partials are the plain problem's (d->cs, scal, flags, part)
     double *cg = nullptr;       // [4 (NO + 2K) + NO + npix + 1]: x, r, p, q | x' | num | the tails' r.r
     hipGraphExec_t batch = nullptr;   // kCgBatch iterations
+    // scratch of the multi-rank pieces (comap_destripe_ground_dist_*), on their first use
+    double *dist = nullptr;     // [NO + 1]: x' | the tails' r.r
 };
 
 namespace {
@@ -511,6 +513,9 @@ __global__ void k_gr_div(const double *__restrict__ num, const double *__restric
 //   k_gr_update: p.q = sum(part_pq, k_dot_part's partials of the offsets) + the tails' p.q;
 //       a = rr / p.q; x += a p; r -= a q; r.r partials of the offsets into part_rr (k_cg_update's
 //       grid), the tails' r.r into tail_rr; block 0 saves rr and p.q
+// SPLIT (the multi-rank pieces, cut at the all-reduces): p.q is read from scal[2], where
+// k_gr_pq left the rank's sum for the caller to all-reduce, and k_gr_rr takes the r.r final.
+template <bool SPLIT>
 __global__ void __launch_bounds__(256) k_gr_update(double *__restrict__ scal, const double *__restrict__ part_pq,
                                                    double *__restrict__ x, double *__restrict__ r,
                                                    const double *__restrict__ p, const double *__restrict__ q,
@@ -519,8 +524,13 @@ __global__ void __launch_bounds__(256) k_gr_update(double *__restrict__ scal, co
 {
     __shared__ double red[4];
     if (gr_done(flags)) return;
-    double pq = block_final_sum(part_pq, kRedBlocks, red);
-    pq += tail_dot(p + NO, q + NO, 2 * K, red);
+    double pq;
+    if constexpr (SPLIT) {
+        pq = scal[2];
+    } else {
+        pq = block_final_sum(part_pq, kRedBlocks, red);
+        pq += tail_dot(p + NO, q + NO, 2 * K, red);
+    }
     const double rr = scal[3];
     const double a[1] = {rr / pq};
     const bool live[1] = {true};
@@ -539,13 +549,19 @@ __global__ void __launch_bounds__(256) k_gr_update(double *__restrict__ scal, co
             t = fma(rv, rv, t);
         }
         t = block_sum(t, red);
-        if (threadIdx.x == 0) { tail_rr[0] = t; scal[1] = rr; scal[2] = pq; }
+        if (threadIdx.x == 0) {
+            tail_rr[0] = t;
+            scal[1] = rr;
+            if constexpr (!SPLIT) scal[2] = pq;
+        }
     }
 }
 
 //   k_gr_direction: rr_new = sum(part_rr) + tail_rr; p = r + (rr_new / rr) p; block 0, after its
 //       own sweep: rr = rr_new, count the iteration, stop when rr_new / rr0 is NaN or below the
 //       threshold (scal / flags: the one-band layout of destriper_internal.h)
+// SPLIT: rr_new is read from scal[3], the all-reduced sum of k_gr_rr's.
+template <bool SPLIT>
 __global__ void __launch_bounds__(256) k_gr_direction(double *__restrict__ scal, const double *__restrict__ part_rr,
                                                       int nrr, const double *__restrict__ tail_rr,
                                                       double *__restrict__ p, const double *__restrict__ r, int64_t NO,
@@ -553,8 +569,13 @@ __global__ void __launch_bounds__(256) k_gr_direction(double *__restrict__ scal,
 {
     __shared__ double red[4];
     if (flags[0]) return;
-    double rrn = block_final_sum(part_rr, nrr, red);
-    rrn += tail_rr[0];
+    double rrn;
+    if constexpr (SPLIT) {
+        rrn = scal[3];
+    } else {
+        rrn = block_final_sum(part_rr, nrr, red);
+        rrn += tail_rr[0];
+    }
     const double beta[1] = {rrn / scal[1]};
     const bool live[1] = {true};
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < NO; i += (int64_t)gridDim.x * blockDim.x)
@@ -562,7 +583,7 @@ __global__ void __launch_bounds__(256) k_gr_direction(double *__restrict__ scal,
     if (blockIdx.x == 0) {
         for (int64_t i = NO + threadIdx.x; i < NO + 2 * K; i += 256) p[i] = r[i] + beta[0] * p[i];
         if (threadIdx.x == 0) {
-            scal[3] = rrn;
+            if constexpr (!SPLIT) scal[3] = rrn;   // (split: other blocks may still be reading it)
             flags[3] += 1;
             flags[1] += 1;
             const double delta = rrn / scal[0];
@@ -571,11 +592,37 @@ __global__ void __launch_bounds__(256) k_gr_direction(double *__restrict__ scal,
     }
 }
 
+// The multi-rank pieces' two scalar finals, one workgroup each, in the order of the eager calls
+// (k_dot_final's sum of the offsets' partials, then the tails' part added):
+//   k_gr_pq: scal[2] = sum(part, comap_destripe_dot's grid) + the tails' p . q
+__global__ void __launch_bounds__(256) k_gr_pq(const double *__restrict__ part, const double *__restrict__ p,
+                                               const double *__restrict__ q, int64_t NO, int64_t K,
+                                               double *__restrict__ scal, const int32_t *__restrict__ flags)
+{
+    __shared__ double red[4];
+    if (gr_done(flags)) return;
+    double pq = block_final_sum(part, kRedBlocks, red);
+    pq += tail_dot(p + NO, q + NO, 2 * K, red);
+    if (threadIdx.x == 0) scal[2] = pq;
+}
+
+//   k_gr_rr: scal[3] = sum(part_rr, comap_destripe_cg_update's grid) + the tails' r . r
+__global__ void __launch_bounds__(256) k_gr_rr(const double *__restrict__ part_rr, int nrr,
+                                               const double *__restrict__ tail_rr, double *__restrict__ scal,
+                                               const int32_t *__restrict__ flags)
+{
+    __shared__ double red[4];
+    if (gr_done(flags)) return;
+    double rrn = block_final_sum(part_rr, nrr, red);
+    rrn += tail_rr[0];
+    if (threadIdx.x == 0) scal[3] = rrn;
+}
+
 void ground_free(comap_ground *g, bool idle)
 {
     if (g->batch) (void)hipGraphExecDestroy(g->batch);
     void *b[] = {g->gint, g->glist, g->wa, g->mu, g->sigma, g->saa, g->ta, g->gpix, g->ga, g->gprow, g->gpk, g->gpa,
-                 g->chunks, g->cgrp, g->part, g->wrapped, g->cg};
+                 g->chunks, g->cgrp, g->part, g->wrapped, g->cg, g->dist};
     comap_tmp_free_on(b, (int)(sizeof(b) / sizeof(b[0])), nullptr, idle);
     delete g;
 }
@@ -937,8 +984,8 @@ static void ground_enqueue_iteration(comap_ground *g, hipStream_t st)
     launch_ground_project(g, st, xp, p + NO, num, d->h, q, q + NO, flags);
     ds_dot_part(d, st, p, q, NO);   // not gated: it writes the partials only
     const unsigned ug = ds_upd_grid(NO);
-    k_gr_update<<<ug, 256, 0, st>>>(d->scal, d->part, x, r, p, q, NO, K, part_rr, tail_rr, flags);
-    k_gr_direction<<<grid_for(NO), 256, 0, st>>>(d->scal, part_rr, (int)ug, tail_rr, p, r, NO, K, flags);
+    k_gr_update<false><<<ug, 256, 0, st>>>(d->scal, d->part, x, r, p, q, NO, K, part_rr, tail_rr, flags);
+    k_gr_direction<false><<<grid_for(NO), 256, 0, st>>>(d->scal, part_rr, (int)ug, tail_rr, p, r, NO, K, flags);
 }
 
 // CG vectors and (small problems, or COMAP_DS_CGGRAPH=1) the kCgBatch-iteration graph, on first use
@@ -1023,5 +1070,85 @@ extern "C" int comap_destripe_ground_solve(comap_ground *g, double threshold, in
     if (weight) COMAP_CHECK(ctx, hipMemcpyAsync(weight, d->h, 8 * (size_t)np, hipMemcpyDeviceToDevice, st));
     if (hits) COMAP_CHECK(ctx, hipMemcpyAsync(hits, d->hits, 8 * (size_t)np, hipMemcpyDeviceToDevice, st));
     COMAP_CHECK(ctx, hipStreamSynchronize(st));
+    return 0;
+}
+
+// ---------------------------------------------------------------- multi-rank CG pieces
+// ground_enqueue_iteration cut at its three cross-rank sums (map numerator, p.q, r.r), on the
+// caller's vectors [x | s | c] and scalars, on the bound stream: the ground counterparts of
+// comap_destripe_dist_bin / _project / _update / _direction.  The launches and their arguments are
+// the native iteration's; only the two scalar finals, which there ride in k_gr_update /
+// k_gr_direction, are kernels of their own (k_gr_pq, k_gr_rr), because an all-reduce follows each.
+// Every local sum keeps the order of the eager per-piece calls, so the iterates equal those of
+// Python's cg_solve on the same ranks bit for bit.
+static int ground_dist_scratch(comap_ground *g)
+{
+    if (g->dist) return 0;
+    return dalloc(g->ctx, &g->dist, (size_t)g->NO + 1) ? -2 : 0;
+}
+
+extern "C" int comap_destripe_ground_dist_bin(comap_ground *g, const double *p, double *num, const int32_t *flags)
+{
+    if (!g || !p || !num || !flags) return -1;
+    COMAP_DEVICE_GUARD(g->ctx);
+    comap_ctx *ctx = g->ctx;
+    comap_destriper *d = g->d;
+    if (const int rc = ground_dist_scratch(g)) return rc;
+    hipStream_t st = ctx->stream;
+    const int64_t NO = g->NO, K = g->K;
+    double *xp = g->dist;
+    k_gr_fold<<<grid_for(NO), 256, 0, st>>>(p, p + NO + K, g->gint, NO, xp, d->cf ? d->wbar : nullptr, d->pt, flags);
+    ds_launch_bin(d, st, d->cf ? d->pt : xp, nullptr, nullptr, num, flags, false, d->cf);
+    k_gr_bin<<<grid_for(g->npix * kBinLanes, 65536), 256, 0, st>>>(g->gprow, g->gpk, g->gpa, p + NO, 1.0, g->npix, num,
+                                                                   flags);
+    COMAP_LAUNCH_CHECK(ctx);
+    return 0;
+}
+
+extern "C" int comap_destripe_ground_dist_project(comap_ground *g, const double *p, const double *num, const double *h,
+                                                  double *q, double *scal, const int32_t *flags)
+{
+    if (!g || !p || !num || !h || !q || !scal || !flags) return -1;
+    COMAP_DEVICE_GUARD(g->ctx);
+    comap_ctx *ctx = g->ctx;
+    comap_destriper *d = g->d;
+    if (!g->dist) return comap_fail(ctx, -1, "ground dist_project: call comap_destripe_ground_dist_bin on p first");
+    hipStream_t st = ctx->stream;
+    const int64_t NO = g->NO, K = g->K;
+    const double *xp = g->dist;
+    ds_launch_project(d, st, xp, num, h, q, flags);
+    launch_ground_project(g, st, xp, p + NO, num, h, q, q + NO, flags);
+    ds_dot_part(d, st, p, q, NO);   // not gated: it writes the partials only
+    k_gr_pq<<<1, 256, 0, st>>>(d->part, p, q, NO, K, scal, flags);
+    COMAP_LAUNCH_CHECK(ctx);
+    return 0;
+}
+
+extern "C" int comap_destripe_ground_dist_update(comap_ground *g, double *scal, double *x, double *r, const double *p,
+                                                 const double *q, const int32_t *flags)
+{
+    if (!g || !scal || !x || !r || !p || !q || !flags) return -1;
+    COMAP_DEVICE_GUARD(g->ctx);
+    comap_ctx *ctx = g->ctx;
+    comap_destriper *d = g->d;
+    if (const int rc = ground_dist_scratch(g)) return rc;
+    hipStream_t st = ctx->stream;
+    const int64_t NO = g->NO, K = g->K;
+    double *part_rr = d->part + kPartMax, *tail_rr = g->dist + NO;
+    const unsigned ug = ds_upd_grid(NO);
+    k_gr_update<true><<<ug, 256, 0, st>>>(scal, nullptr, x, r, p, q, NO, K, part_rr, tail_rr, flags);
+    k_gr_rr<<<1, 256, 0, st>>>(part_rr, (int)ug, tail_rr, scal, flags);
+    COMAP_LAUNCH_CHECK(ctx);
+    return 0;
+}
+
+extern "C" int comap_destripe_ground_dist_direction(comap_ground *g, double *scal, double *p, const double *r,
+                                                    int32_t *flags)
+{
+    if (!g || !scal || !p || !r || !flags) return -1;
+    COMAP_DEVICE_GUARD(g->ctx);
+    comap_ctx *ctx = g->ctx;
+    k_gr_direction<true><<<grid_for(g->NO), 256, 0, ctx->stream>>>(scal, nullptr, 0, nullptr, p, r, g->NO, g->K, flags);
+    COMAP_LAUNCH_CHECK(ctx);
     return 0;
 }

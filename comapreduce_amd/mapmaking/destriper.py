@@ -219,6 +219,47 @@ def _dist_iteration(ops, allreduce, p, num, h, q, scal, flags, x, r):
     return pieces
 
 
+def cg_solve_ground_batched(g, allreduce, threshold=1e-6, niter=100, batch=16):
+    """Multi-rank CG of the ground-template operator (``GroundOps``): the iterates of
+    ``cg_solve(g, allreduce)`` bit for bit -- the same launches, local summation orders and
+    cross-rank sums -- with the stop test on the device (comap_destripe_ground_dist_*), so
+    ``batch`` iterations are queued per host read of the flags: 4 native calls and 3
+    all-reduces (num, scal[2:3], scal[3:4]) per iteration instead of 11 calls, 3 all-reduces
+    and a blocking read of r.r.  Each rank holds whole (observation, feed) groups, so its
+    offsets, slopes and levels are rank-local; iterations queued after the stop are no-ops.
+    Returns (u = [x internal order | s | c], iterations, h, nnum) like ``cg_solve``."""
+    h0, _, n0 = g.local_maps()
+    h = allreduce(h0)
+    nnum = allreduce(n0)
+    n = g.n_offsets
+    x, r, q = g.zeros(n), g.zeros(n), g.zeros(n)
+    num = g.zeros(g.npix)
+    g.project(None, nnum, h, r)                  # b, ground tail included; r = p = b (u0 = 0)
+    p = g.copy(r)
+    scal = g.zeros(5)                            # rr0, rr, pq, rr_new, threshold
+    g.dot(r, r, scal[0:1])
+    allreduce(scal[0:1])
+    scal[1:2].copy_(scal[0:1])
+    scal[3:4].copy_(scal[0:1])
+    scal[4] = float(threshold)
+    flags = g.torch.zeros(4, dtype=g.torch.int32, device=g.dev)
+    enq = 0
+    while enq < niter:
+        k = min(batch, niter - enq)
+        for _ in range(k):
+            g.dist_bin(p, num, flags)
+            allreduce(num)
+            g.dist_project(p, num, h, q, scal, flags)
+            allreduce(scal[2:3])
+            g.dist_update(scal, x, r, p, q, flags)
+            allreduce(scal[3:4])
+            g.dist_direction(scal, p, r, flags)
+        enq += k
+        if int(flags[0].item()):
+            break
+    return x, int(flags[3].item()), h, nnum
+
+
 def cg_solve_graph(ops, allreduce, threshold=1e-6, niter=100, batch=16):
     """cg_solve_batched with each batch of ``batch`` iterations -- the four kernel
     pieces AND the three all-reduces of every iteration -- captured once into a
@@ -545,6 +586,55 @@ def ground_groups(feedid, obsids, offset_length):
     return gid[:, 0].astype(np.int32), uobs, ufeed
 
 
+def merge_ground_tables(tables):
+    """One ground-fit table from every rank's: the table a single rank holding all samples
+    would report.  ``tables``: per rank {'obsids' [n_obs], 'feeds' [n_feeds], 'slope', 'level',
+    'wrapped', 'held' [n_obs, n_feeds]} over the rank's own np.unique grids, 'held' marking the
+    (observation, feed) pairs the rank has samples of.  The result spans the union of
+    observations x the union of feeds, both sorted; a pair no rank holds is 0 / not wrapped.
+    ValueError when two ranks hold the same pair: its template must live on one rank, or it
+    would be fitted twice."""
+    obs = [np.asarray(t['obsids']).reshape(-1) for t in tables]
+    feeds = [np.asarray(t['feeds']).reshape(-1) for t in tables]
+    uobs = np.unique(np.concatenate(obs)) if obs else np.zeros(0)
+    ufeed = np.unique(np.concatenate(feeds)) if feeds else np.zeros(0)
+    shape = (uobs.size, ufeed.size)
+    out = {'obsids': uobs, 'feeds': ufeed, 'slope': np.zeros(shape), 'level': np.zeros(shape),
+           'wrapped': np.zeros(shape, bool)}
+    owner = np.full(shape, -1, np.int64)
+    for rank, t in enumerate(tables):
+        held = np.asarray(t['held'], bool).reshape(obs[rank].size, feeds[rank].size)
+        io, jf = np.nonzero(held)
+        gi, gj = np.searchsorted(uobs, obs[rank])[io], np.searchsorted(ufeed, feeds[rank])[jf]
+        twice = owner[gi, gj] >= 0
+        if np.any(twice):
+            k = int(np.nonzero(twice)[0][0])
+            raise ValueError(f'observation {uobs[gi[k]]}, feed {ufeed[gj[k]]} has samples on ranks '
+                             f'{int(owner[gi[k], gj[k]])} and {rank}: the ground template of one (observation, feed) '
+                             'must live on one rank')
+        owner[gi, gj] = rank
+        for key in ('slope', 'level', 'wrapped'):
+            if t.get(key) is not None:
+                out[key][gi, gj] = np.asarray(t[key]).reshape(held.shape)[io, jf]
+    return out
+
+
+def _ranks_agree(d, error, held=None):
+    """Every rank's set-up status exchanged, so that all ranks raise or none does (a rank
+    that raised alone would leave its peers waiting in the next collective).  error: this
+    rank's exception or None; held: its populated-pair table for merge_ground_tables'
+    duplicate check, which then also fails on every rank."""
+    mine = (None if error is None else (type(error).__name__, str(error)), held)
+    everyone = [None] * d.get_world_size()
+    d.all_gather_object(everyone, mine)
+    for rank, (err, _) in enumerate(everyone):
+        if err is not None:
+            if rank == d.get_rank():
+                raise error
+            raise ValueError(f'ground template set-up failed on rank {rank}: {err[0]}: {err[1]}')
+    merge_ground_tables([t for _, t in everyone])
+
+
 class GroundOps:
     """The destriper operator with a ground (azimuth) template per (observation, feed):
     the reference's op_Ax_with_ground (Destriper.py:265-336) as the operator object that
@@ -684,6 +774,23 @@ class GroundOps:
         self._c('comap_destripe_ground_tail_direction', self.g, self.ops._s(rr_new), self.ops._s(rr), self._tail(p),
                 self._tail(r))
 
+    # ---- multi-rank iteration pieces (device stop flags; see cg_solve_ground_batched)
+    def dist_bin(self, p, num, flags):
+        self._folded = None
+        self._c('comap_destripe_ground_dist_bin', self.g, N.dptr(self._u(p)), self.ops._m(num), self.ops._f(flags))
+
+    def dist_project(self, p, num, h, q, scal, flags):
+        self._c('comap_destripe_ground_dist_project', self.g, N.dptr(self._u(p)), self.ops._m(num), self.ops._m(h),
+                N.dptr(self._u(q)), self.ops._s(scal, 5), self.ops._f(flags))
+
+    def dist_update(self, scal, x, r, p, q, flags):
+        self._c('comap_destripe_ground_dist_update', self.g, self.ops._s(scal, 5), N.dptr(self._u(x)),
+                N.dptr(self._u(r)), N.dptr(self._u(p)), N.dptr(self._u(q)), self.ops._f(flags))
+
+    def dist_direction(self, scal, p, r, flags):
+        self._c('comap_destripe_ground_dist_direction', self.g, self.ops._s(scal, 5), N.dptr(self._u(p)),
+                N.dptr(self._u(r)), self.ops._f(flags))
+
     # ---- single-rank native solve (no Python per iteration)
     def solve_native(self, threshold, niter):
         """comap_destripe_ground_solve: (u [N/L + 2K] = x internal order | s | c, iterations,
@@ -727,6 +834,12 @@ def copy_stream(dev):
         cs = _COPY_STREAMS[key] = torch.cuda.Stream(dev)
     return cs
 
+
+# The ground solve's driver across ranks when COMAP_DS_GROUND_SOLVE is not set: 'batched'
+# (cg_solve_ground_batched) or 'eager' (cg_solve).  Eager until the batched driver measures
+# faster outside the rounds' spread: with two gloo ranks on one GPU it did at one observation per
+# rank and did not at four; no multi-GPU figure exists yet.
+GROUND_RANKS_SOLVE = 'eager'
 
 TILE = 8     # map layout tile (pixels per side) for a known map shape; COMAP_DS_TILE=0: row-major
 
@@ -774,7 +887,12 @@ class DeviceDestriper:
     mapmaking/rankplan.py models both (COMAP_DS_RANKS=auto: small problems such as one
     observation (C4) are latency-bound across ranks and are gathered, large ones (C5)
     sharded).  The default is COMAP_DS_RANKS=shard until a multi-GPU run replaces the
-    model's assumed all-reduce latency and bandwidth; gather forces the other."""
+    model's assumed all-reduce latency and bandwidth; gather forces the other.
+
+    With ``ground=`` across ranks the problem is always sharded, whatever COMAP_DS_RANKS says
+    (``gather`` and ``auto`` are not supported with the ground template; a ``gather`` request
+    falls back to shard with a warning): every rank must hold whole (observation, feed)
+    groups, whose offsets, slopes and levels are then rank-local unknowns."""
 
     def __init__(self, pixels, tod, weights, offset_length, npix, device=None, keep=None, map_shape=None,
                  ground=None):
@@ -783,8 +901,11 @@ class DeviceDestriper:
         come back in the caller's order.
         ground (az, feedid, obsids), per sample: also fit an azimuth slope and a level per
         (observation, feed) jointly with the offsets (GroundOps; the reference's
-        op_Ax_with_ground, Destriper.py:265-336).  solve() then adds res['ground'].  The fit is
-        per file and feed, hence local to a rank: one band on one rank only."""
+        op_Ax_with_ground, Destriper.py:265-336).  solve() then adds res['ground'].  One band.
+        The fit is per file and feed, hence local to the rank that holds the file: across ranks
+        every (observation, feed) must lie on one rank (ValueError on every rank otherwise, as
+        for any rank's set-up error), and rank 0's res['ground'] is the merged table of all
+        ranks (merge_ground_tables; None on the others)."""
         self.layout, self.okey = None, None
         self.ground = None
         T = int(os.environ.get('COMAP_DS_TILE', str(TILE)))
@@ -804,10 +925,12 @@ class DeviceDestriper:
         if ground is not None:
             if self.multi:
                 raise NotImplementedError('the ground template solves one band: pass a 1-D tod')
-            if d is not None and d.get_world_size() > 1:
-                raise NotImplementedError('the ground template is not wired across ranks (sharded or gathered)')
-        if d is not None and d.get_world_size() > 1:
-            if self._choose_gather(d, pixels, tod, offset_length):
+        ranks = d is not None and d.get_world_size() > 1
+        if ground is not None and ranks and os.environ.get('COMAP_DS_RANKS', 'shard') == 'gather':
+            import warnings
+            warnings.warn('COMAP_DS_RANKS=gather is not supported with the ground template: sharding')
+        if ranks:
+            if ground is None and self._choose_gather(d, pixels, tod, offset_length):
                 self._gather(d, pixels, tod, weights, keep, offset_length, npix, device)
                 return
             if os.environ.get('COMAP_DS_COMPACT', '1') != '0':
@@ -815,8 +938,20 @@ class DeviceDestriper:
         self.ops = N.retry_oom(DeviceOps, pixels, tod, weights, offset_length, npix, device, keep, self.okey)
         if ground is not None:
             az, feedid, obsids = ground
-            gid, uobs, ufeed = ground_groups(feedid, obsids, offset_length)
-            self.gops = N.retry_oom(GroundOps, self.ops, az, gid, uobs.size * ufeed.size)
+            # across ranks, a rank that raised here alone would leave its peers in a collective:
+            # its local set-up error is held back and _ranks_agree raises on every rank, or on none
+            error, table = None, None
+            try:
+                gid, uobs, ufeed = ground_groups(feedid, obsids, offset_length)
+                self.held = (np.bincount(gid, minlength=uobs.size * ufeed.size) > 0).reshape(uobs.size, ufeed.size)
+                table = {'obsids': uobs, 'feeds': ufeed, 'held': self.held}
+                self.gops = N.retry_oom(GroundOps, self.ops, az, gid, uobs.size * ufeed.size)
+            except (ValueError, IndexError) as e:
+                if not ranks:
+                    raise
+                error = e
+            if ranks:
+                _ranks_agree(d, error, table)
             self.ground = (uobs, ufeed)
 
     # ---- rank policy
@@ -1065,6 +1200,9 @@ class DeviceDestriper:
         arrays [n_obs, n_feeds], GroundOps.fit's units; 'wrapped': the group crosses azimuth
         0 / 360 and was fitted on az + 360 where az < 180); 'x' holds the offsets."""
         ops, g = self.ops, self.gops
+        d = _dist()
+        if d is not None and d.get_world_size() > 1:
+            return self._solve_ground_ranks(d, threshold, niter, to_host)
         mode = os.environ.get('COMAP_DS_GROUND_SOLVE', 'native')
         if mode == 'eager':
             u, it, h, nnum = cg_solve(g, lambda t: t, threshold, niter)
@@ -1088,6 +1226,46 @@ class DeviceDestriper:
         return {'x': ops.natural(u), 'iters': it, 'maps': maps_to_host(maps) if to_host else maps,
                 'ground': {'obsids': uobs, 'feeds': ufeed, 'slope': slope, 'level': level, 'wrapped': wrapped},
                 'solution': u}
+
+
+    def _solve_ground_ranks(self, d, threshold, niter, to_host):
+        """_solve_ground across ranks (sharded), on the rank's own groups: the eager
+        ``cg_solve`` with the sharded all-reduces (the default, GROUND_RANKS_SOLVE) or, with
+        COMAP_DS_GROUND_SOLVE=batched, ``cg_solve_ground_batched`` (device stop test, 16
+        iterations per host check; the same iterates bit for bit); the maps from the
+        all-reduced numerator, hits and the global weight map.  'x' and 'solution' stay
+        rank-local; 'ground' is the merged table on rank 0, None elsewhere."""
+        ops, g = self.ops, self.gops
+        mode = os.environ.get('COMAP_DS_GROUND_SOLVE', GROUND_RANKS_SOLVE)
+        if mode == 'eager':
+            u, it, h, nnum = cg_solve(g, torch_allreduce, threshold, niter)
+        elif mode in ('batched', 'native'):
+            u, it, h, nnum = cg_solve_ground_batched(g, torch_allreduce, threshold, niter)
+        else:
+            raise ValueError(f"COMAP_DS_GROUND_SOLVE must be 'batched' (or 'native') or 'eager', not {mode!r}")
+        _, hits, _ = ops.local_maps()
+        torch_allreduce(hits)
+        num = ops.zeros(ops.npix)
+        g.bin(u, 1, num)                 # the rank's naive numerator - W x' - ground bin(s)
+        torch_allreduce(num)
+        maps = {'map': ops.zeros(ops.npix), 'naive': ops.zeros(ops.npix), 'weight': h, 'hits': hits}
+        ops.div_map(num, h, maps['map'])
+        ops.div_map(nnum, h, maps['naive'])
+        maps = {k: self._expand(v) for k, v in maps.items()}
+        if self.layout is not None:
+            maps = {k: self._untile(v, 1) for k, v in maps.items()}
+        maps['map2'] = maps['weight']
+        uobs, ufeed = self.ground
+        slope, level = (v.cpu().numpy().reshape(uobs.size, ufeed.size) for v in g.fit(u))
+        wrapped = g.wrapped.cpu().numpy().reshape(uobs.size, ufeed.size) != 0
+        tables = [None] * d.get_world_size()
+        d.all_gather_object(tables, {'obsids': uobs, 'feeds': ufeed, 'slope': slope, 'level': level,
+                                     'wrapped': wrapped, 'held': self.held})
+        rank = d.get_rank()
+        if to_host:
+            maps = maps_to_host(maps) if rank == 0 else None
+        return {'x': ops.natural(u), 'iters': it, 'maps': maps,
+                'ground': merge_ground_tables(tables) if rank == 0 else None, 'solution': u}
 
 
 def maps_to_host(maps):
@@ -1117,7 +1295,9 @@ def run_destriper(_pointing, _tod, _weights, offset_length, pixel_edges, az=None
     ground=True, an extension: fit an azimuth slope and a level per (observation, feed)
     from ``az``, ``feedid`` and ``obsids`` jointly with the offsets (the reference's
     op_Ax_with_ground, :265-336, which its run() leaves switched off); the result gains
-    'Ground': {'obsids', 'feeds', 'slope', 'level'} (one rank only)."""
+    'Ground': {'obsids', 'feeds', 'slope', 'level', 'wrapped'}: across ranks (every
+    (observation, feed) on one rank) rank 0 gets the merged table of all ranks' observations
+    and the other ranks None maps and 'Ground': None."""
     if special_weight is not None:
         raise NotImplementedError('special_weight is unused by run_destriper in the reference (:482)')
     import torch
@@ -1131,6 +1311,8 @@ def run_destriper(_pointing, _tod, _weights, offset_length, pixel_edges, az=None
                              np.asarray(_weights, dtype=np.float64), int(offset_length), npix, device,
                              map_shape=map_shape, ground=(np.asarray(az, dtype=np.float64), feedid, obsids))
         res = dd.solve(threshold, niter, to_host=True)
+        if res['maps'] is None:          # a rank other than 0
+            return {'All': {'map': None, 'naive': None, 'weight': None, 'map2': None}, 'Ground': None}
         return {'All': res['maps'], 'Ground': res['ground']}
     dd = DeviceDestriper(np.asarray(_pointing), np.asarray(_tod, dtype=np.float64),
                          np.asarray(_weights, dtype=np.float64), int(offset_length), npix, device, map_shape=map_shape)

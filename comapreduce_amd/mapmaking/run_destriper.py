@@ -137,7 +137,10 @@ def main(filelistname, offset_length=50, feed_weights=None, prefix='fg9', output
     slope and a level per (observation, feed) jointly with the offsets (the reference's
     op_Ax_with_ground, Destriper.py:265-336, which its run() leaves switched off).  This
     takes the per-band loop, which reads az / feedid / obsids; rank 0 writes each band's fit
-    to <output_dir>/<prefix>_ground_band<iband>.npz and the band's entry gains 'Ground'."""
+    -- across ranks the merged table of all ranks' observations -- to
+    <output_dir>/<prefix>_ground_band<iband>.npz and the band's entry gains 'Ground' (None on
+    the other ranks).  Files are whole observations, so each (observation, feed) lies on the
+    one rank that holds the file."""
     rank, size = _rank_size()
     if device is None:
         import torch

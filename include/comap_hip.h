@@ -434,6 +434,35 @@ int comap_destripe_ground_tail_direction(comap_ground *g, const double *rr_new_d
  * NULL).  niter < 0 or a NULL g / u_dev: -1.  Synchronises. */
 int comap_destripe_ground_solve(comap_ground *g, double threshold, int32_t niter, double *u_dev, double *map_dev,
                                 double *naive_dev, double *weight_dev, double *hits_dev, int32_t *iters_out);
+/* The ground solve's iteration split at the three cross-rank sums the caller performs between the
+ * calls: the ground counterparts of comap_destripe_dist_bin / _project / _update / _direction, for
+ * ranks that each hold whole (observation, feed) groups (slopes, levels and offsets are then
+ * rank-local unknowns; only the map numerator and the two CG scalars cross ranks).  Vectors are the
+ * caller's, whole: f64 [N/L + 2K] = x (internal offset order) | s | c.  scal_dev f64 [5]: rr0, rr,
+ * pq, rr_new, threshold, with rr and rr_new initialised to rr0; flags_dev int32 [4]: stop,
+ * iterations, stop, iterations (the one-band layout above).  On the bound stream, no host sync;
+ * every launch but the pure partial-sum ones returns at once when flags[0] is set, so a batch of
+ * iterations can be queued per host check of flags:
+ *   ground_dist_bin        x' = p + c[g(o)]; num = W x' + ground bin(s): the rank's undivided
+ *                          numerator (every pixel row, as comap_destripe_bin) -> all-reduce num
+ *   ground_dist_project    q = A p from the GLOBAL num and h (m = num / h on the fly), on the x' of
+ *                          the ground_dist_bin call before it (same p); scal[2] = the rank's p . q
+ *                                                                          -> all-reduce scal[2]
+ *   ground_dist_update     alpha = rr_new / scal[2]; x += alpha p; r -= alpha q; rr = rr_new;
+ *                          scal[3] = the rank's r . r                      -> all-reduce scal[3]
+ *   ground_dist_direction  p = r + (scal[3] / rr) p; count the iteration; stop when scal[3] / rr0
+ *                          is NaN or below the threshold.
+ * Every local sum is taken in the order of the per-piece calls (comap_destripe_dot's partial grid
+ * and final, then the tail's dot added; comap_destripe_cg_update's grid, then the tail), so the
+ * iterates equal those of Python's cg_solve on the same ranks bit for bit. */
+int comap_destripe_ground_dist_bin(comap_ground *g, const double *p_dev, double *num_dev, const int32_t *flags_dev);
+int comap_destripe_ground_dist_project(comap_ground *g, const double *p_dev, const double *num_dev,
+                                       const double *h_dev, double *q_dev, double *scal_dev,
+                                       const int32_t *flags_dev);
+int comap_destripe_ground_dist_update(comap_ground *g, double *scal_dev, double *x_dev, double *r_dev,
+                                      const double *p_dev, const double *q_dev, const int32_t *flags_dev);
+int comap_destripe_ground_dist_direction(comap_ground *g, double *scal_dev, double *p_dev, const double *r_dev,
+                                         int32_t *flags_dev);
 
 /* ------------------------------------------------------------ destriper data prep (COMAPData.py) */
 /* One Level-2 file's inputs to comap_prep_gather (device pointers).  Output row r
