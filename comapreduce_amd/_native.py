@@ -63,9 +63,6 @@ _SIGS = {
     'comap_destripe_create': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int64,
                                       ctypes.POINTER(c_void_p)]),
     'comap_destripe_dist_bin': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
-    'comap_destripe_dist_project': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    'comap_destripe_dist_update': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    'comap_destripe_dist_direction': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'comap_destripe_dist_parts': (c_int32, []),
     'comap_destripe_dist_project_parts': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                   c_void_p]),

@@ -483,7 +483,7 @@ __global__ void __launch_bounds__(256) k_cg_update(const double *__restrict__ rr
 // End-of-iteration bookkeeping (Destriper.py:136-152) by one thread, per band still
 // running: rr = rr_new, count it, stop when delta = rr_new / rr0 is NaN or below the
 // threshold; flags[1] counts iterations any band ran, flags[0] = every band stopped.
-template <int NB, bool kSetRr = true>
+template <int NB>
 __device__ __forceinline__ void cg_check(double *__restrict__ scal, int32_t *__restrict__ flags, const double *rrn)
 {
     bool any = false, all = true;
@@ -491,7 +491,6 @@ __device__ __forceinline__ void cg_check(double *__restrict__ scal, int32_t *__r
     for (int b = 0; b < NB; ++b) {
         if (!flags[2 + b]) {
             any = true;
-            if (kSetRr) scal[NB + b] = rrn[b];   // the per-piece update reads rr there
             scal[3 * NB + b] = rrn[b];
             flags[2 + NB + b] += 1;
             const double delta = rrn[b] / scal[b];
@@ -565,7 +564,7 @@ __global__ void __launch_bounds__(256) k_cg_direction_fused(double *__restrict__
     // block 0 only, after its own sweep: a band that stops here never reads p again.
     // scal[NB+b] is left alone -- other blocks may still be reading it for beta; the
     // fused update takes rr from scal[3NB+b] and rewrites scal[NB+b] itself.
-    if (blockIdx.x == 0 && threadIdx.x == 0) cg_check<NB, false>(scal, flags, rrn);
+    if (blockIdx.x == 0 && threadIdx.x == 0) cg_check<NB>(scal, flags, rrn);
 }
 
 // p = r + (rr_new / rr) p per band still running
@@ -580,16 +579,6 @@ __global__ void k_cg_direction(const double *__restrict__ rr_new, const double *
     for (int b = 0; b < NB; ++b) { beta[b] = rr_new[b] / rr[b]; live[b] = !band_stopped(flags, b); }
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
         direction_row<NB>(p + i * NB, r + i * NB, beta, live);
-}
-
-template <int NB>
-__global__ void k_cg_check(double *__restrict__ scal, int32_t *__restrict__ flags)
-{
-    if (threadIdx.x != 0 || flags[0]) return;
-    double rrn[NB];
-#pragma unroll
-    for (int b = 0; b < NB; ++b) rrn[b] = scal[3 * NB + b];
-    cg_check<NB>(scal, flags, rrn);
 }
 
 __global__ void k_div_map(const double *__restrict__ num, const double *__restrict__ h, int64_t n,
@@ -749,6 +738,11 @@ void ds_dot_part(comap_destriper *d, hipStream_t st, const double *a, const doub
 
 unsigned ds_upd_grid(int64_t NO) { return upd_grid(NO); }
 
+void ds_div_map(hipStream_t st, const double *num, const double *h, int64_t n, double *out)
+{
+    k_div_map<<<grid_for(n), 256, 0, st>>>(num, h, n, out);
+}
+
 extern "C" int comap_destripe_destroy(comap_destriper *d)
 {
     if (!d) return 0;
@@ -894,51 +888,10 @@ extern "C" int comap_destripe_dist_bin(comap_destriper *d, const double *p, doub
     return 0;
 }
 
-extern "C" int comap_destripe_dist_project(comap_destriper *d, const double *p, const double *num, const double *h,
-                                           double *q, double *scal, const int32_t *flags)
-{
-    if (!d || !p || !num || !h || !q || !scal || !flags) return -1;
-    COMAP_DEVICE_GUARD(d->ctx);
-    comap_ctx *ctx = d->ctx;
-    const int nb = d->nb;
-    const unsigned pg = launch_project(d, ctx->stream, p, num, h, q, d->part, flags);
-    COMAP_NB_SWITCH(nb, k_dot_final<NB><<<1, 256, 0, ctx->stream>>>(d->part, (int)pg, scal + 2 * nb, flags));
-    COMAP_LAUNCH_CHECK(ctx);
-    return 0;
-}
-
-extern "C" int comap_destripe_dist_update(comap_destriper *d, double *scal, double *x, double *r, const double *p,
-                                          const double *q, const int32_t *flags)
-{
-    if (!d || !scal || !x || !r || !p || !q || !flags) return -1;
-    COMAP_DEVICE_GUARD(d->ctx);
-    comap_ctx *ctx = d->ctx;
-    const int nb = d->nb;
-    COMAP_NB_SWITCH(nb, k_cg_update<NB><<<upd_grid(d->NO), 256, 0, ctx->stream>>>(scal + nb, scal + 2 * nb, x, r, p, q,
-                                                                              d->NO, d->part, flags);
-                    k_dot_final<NB><<<1, 256, 0, ctx->stream>>>(d->part, (int)upd_grid(d->NO), scal + 3 * nb, flags));
-    COMAP_LAUNCH_CHECK(ctx);
-    return 0;
-}
-
-extern "C" int comap_destripe_dist_direction(comap_destriper *d, double *scal, double *p, const double *r,
-                                             int32_t *flags)
-{
-    if (!d || !scal || !p || !r || !flags) return -1;
-    COMAP_DEVICE_GUARD(d->ctx);
-    comap_ctx *ctx = d->ctx;
-    const int nb = d->nb;
-    COMAP_NB_SWITCH(nb, k_cg_direction<NB><<<grid_for(d->NO), 256, 0, ctx->stream>>>(scal + 3 * nb, scal + nb, p, r,
-                                                                                      d->NO, flags);
-                    k_cg_check<NB><<<1, 64, 0, ctx->stream>>>(scal, flags));
-    COMAP_LAUNCH_CHECK(ctx);
-    return 0;
-}
-
-// Partial-sum variant of the multi-rank pieces: the native solve's kernels, with the p.q
-// and r.r block partials (one slot per block, kDistParts per band, zero beyond the grid)
-// all-reduced between them instead of final sums.  Adding the zero slots changes no bit,
-// so on one rank the iterates equal comap_destripe_solve's.
+// The rest of the iteration is the native solve's kernels, with the p.q and r.r block
+// partials (one slot per block, kDistParts per band, zero beyond the grid) all-reduced
+// between them.  Adding the zero slots changes no bit, so on one rank the iterates equal
+// comap_destripe_solve's.
 constexpr int kDistParts = 1024;   // >= kProjBlocks, kUpdBlocks
 static_assert(kDistParts >= kProjBlocks && kDistParts >= kUpdBlocks, "partial slots");
 
@@ -992,7 +945,7 @@ static void enqueue_iteration(comap_destriper *d, hipStream_t st)
     // (count form: it bins pt = wbar o p, which the previous direction kernel wrote)
     launch_bin(d, st, d->cf ? d->pt : p, nullptr, d->h, num, flags, true, d->cf);   // empty rows of num stay 0
     // 4 launches per iteration: the p.q / r.r finals and the stop test are folded into
-    // the update and direction kernels (same arithmetic and order as k_dot_final + k_cg_check)
+    // the update and direction kernels (k_dot_final's summation order)
     const unsigned pg = launch_project(d, st, p, num, nullptr, q, d->part, flags);
     double *part_rr = d->part + (size_t)d->nb * kPartMax;
     COMAP_NB_SWITCH(d->nb,

@@ -495,14 +495,6 @@ __global__ void __launch_bounds__(256) k_gr_tail_direction(const double *__restr
     for (int64_t i = threadIdx.x; i < n; i += 256) p[i] = r[i] + beta * p[i];
 }
 
-// out_p = num_p / h_p (num_p where h_p == 0)
-__global__ void k_gr_div(const double *__restrict__ num, const double *__restrict__ h, int64_t n,
-                         double *__restrict__ out)
-{
-    for (int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; p < n; p += (int64_t)gridDim.x * blockDim.x)
-        out[p] = map_value(num, h, p);
-}
-
 // The native solve's update and direction over whole vectors [x | s | c]: the arithmetic and the
 // summation orders of the eager driver's calls -- comap_destripe_dot / _cg_update / _cg_direction
 // on the NO offsets, then the one-workgroup tail kernels above on the 2K tail values -- so the
@@ -959,12 +951,37 @@ extern "C" int comap_destripe_ground_tail_direction(comap_ground *g, const doubl
     return 0;
 }
 
+// The matvec q = A p of the native iteration and of the multi-rank pieces, cut where the map
+// numerator is summed across ranks.  First half: x' = p + c[g(o)] (count form: and the bin's
+// input pt = wbar o x'), num = W x' (undivided), then the ground bin.
+static void launch_fold_bin(comap_ground *g, hipStream_t st, const double *p, double *xp, double *num,
+                            const int32_t *flags)
+{
+    comap_destriper *d = g->d;
+    const int64_t NO = g->NO;
+    k_gr_fold<<<grid_for(NO), 256, 0, st>>>(p, p + NO + g->K, g->gint, NO, xp, d->cf ? d->wbar : nullptr, d->pt, flags);
+    // (every row, as comap_destripe_bin: the hit-row bin sizes its lanes differently, another summation order)
+    ds_launch_bin(d, st, d->cf ? d->pt : xp, nullptr, nullptr, num, flags, false, d->cf);
+    k_gr_bin<<<grid_for(g->npix * kBinLanes, 65536), 256, 0, st>>>(g->gprow, g->gpk, g->gpa, p + NO, 1.0, g->npix, num,
+                                                                   flags);
+}
+
+// second half: q = the projection (m = num / h on the fly), the ground projection, then the
+// offsets' p.q partials on the finished q (d->part)
+static void launch_project_dot(comap_ground *g, hipStream_t st, const double *p, const double *xp, const double *num,
+                               const double *h, double *q, const int32_t *flags)
+{
+    const int64_t NO = g->NO;
+    ds_launch_project(g->d, st, xp, num, h, q, flags);
+    launch_ground_project(g, st, xp, p + NO, num, h, q, q + NO, flags);
+    ds_dot_part(g->d, st, p, q, NO);   // not gated: it writes the partials only
+}
+
 // ---------------------------------------------------------------- device-resident ground CG
 // One CG iteration on the ground object's own vectors u = [x | s | c] (n = NO + 2K values each):
-// the launches of the eager driver's iteration with their arguments -- fold, bin (undivided; m =
-// num / h on the fly in the projection and in k_gr_parts), ground bin, projection, ground
-// projection, the offsets' p.q partials on the finished q -- and its dot finals, update, tail
-// update, direction, tail direction and stop test folded into k_gr_update / k_gr_direction.
+// the launches of the eager driver's matvec with their arguments (launch_fold_bin,
+// launch_project_dot), and its dot finals, update, tail update, direction, tail direction and
+// stop test folded into k_gr_update / k_gr_direction.
 // 9 launches (the count form's scaling rides in the fold), all but the partials' gated by the
 // stop flag; the iterates are the eager driver's bit for bit.
 static void ground_enqueue_iteration(comap_ground *g, hipStream_t st)
@@ -974,15 +991,8 @@ static void ground_enqueue_iteration(comap_ground *g, hipStream_t st)
     double *x = g->cg, *r = x + n, *p = r + n, *q = p + n, *xp = q + n, *num = xp + NO, *tail_rr = num + g->npix;
     int32_t *flags = d->flags;
     double *part_rr = d->part + kPartMax;
-    // x' = p + c[g(o)] (count form: and the bin's input pt = wbar o x')
-    k_gr_fold<<<grid_for(NO), 256, 0, st>>>(p, p + NO + K, g->gint, NO, xp, d->cf ? d->wbar : nullptr, d->pt, flags);
-    // (every row, as comap_destripe_bin: the hit-row bin sizes its lanes differently, another summation order)
-    ds_launch_bin(d, st, d->cf ? d->pt : xp, nullptr, nullptr, num, flags, false, d->cf);
-    k_gr_bin<<<grid_for(g->npix * kBinLanes, 65536), 256, 0, st>>>(g->gprow, g->gpk, g->gpa, p + NO, 1.0, g->npix, num,
-                                                                   flags);
-    ds_launch_project(d, st, xp, num, d->h, q, flags);
-    launch_ground_project(g, st, xp, p + NO, num, d->h, q, q + NO, flags);
-    ds_dot_part(d, st, p, q, NO);   // not gated: it writes the partials only
+    launch_fold_bin(g, st, p, xp, num, flags);
+    launch_project_dot(g, st, p, xp, num, d->h, q, flags);
     const unsigned ug = ds_upd_grid(NO);
     k_gr_update<false><<<ug, 256, 0, st>>>(d->scal, d->part, x, r, p, q, NO, K, part_rr, tail_rr, flags);
     k_gr_direction<false><<<grid_for(NO), 256, 0, st>>>(d->scal, part_rr, (int)ug, tail_rr, p, r, NO, K, flags);
@@ -1063,9 +1073,9 @@ extern "C" int comap_destripe_ground_solve(comap_ground *g, double threshold, in
         ds_launch_bin(d, st, xp, d->nnum, nullptr, num, nullptr, false, false);
         k_gr_bin<<<grid_for(np * kBinLanes, 65536), 256, 0, st>>>(g->gprow, g->gpk, g->gpa, x + NO, -1.0, np, num,
                                                                   nullptr);
-        k_gr_div<<<grid_for(np), 256, 0, st>>>(num, d->h, np, map);
+        ds_div_map(st, num, d->h, np, map);
     }
-    if (naive) k_gr_div<<<grid_for(np), 256, 0, st>>>(d->nnum, d->h, np, naive);
+    if (naive) ds_div_map(st, d->nnum, d->h, np, naive);
     COMAP_LAUNCH_CHECK(ctx);
     if (weight) COMAP_CHECK(ctx, hipMemcpyAsync(weight, d->h, 8 * (size_t)np, hipMemcpyDeviceToDevice, st));
     if (hits) COMAP_CHECK(ctx, hipMemcpyAsync(hits, d->hits, 8 * (size_t)np, hipMemcpyDeviceToDevice, st));
@@ -1075,8 +1085,7 @@ extern "C" int comap_destripe_ground_solve(comap_ground *g, double threshold, in
 
 // ---------------------------------------------------------------- multi-rank CG pieces
 // ground_enqueue_iteration cut at its three cross-rank sums (map numerator, p.q, r.r), on the
-// caller's vectors [x | s | c] and scalars, on the bound stream: the ground counterparts of
-// comap_destripe_dist_bin / _project / _update / _direction.  The launches and their arguments are
+// caller's vectors [x | s | c] and scalars, on the bound stream.  The launches and their arguments are
 // the native iteration's; only the two scalar finals, which there ride in k_gr_update /
 // k_gr_direction, are kernels of their own (k_gr_pq, k_gr_rr), because an all-reduce follows each.
 // Every local sum keeps the order of the eager per-piece calls, so the iterates equal those of
@@ -1092,15 +1101,8 @@ extern "C" int comap_destripe_ground_dist_bin(comap_ground *g, const double *p, 
     if (!g || !p || !num || !flags) return -1;
     COMAP_DEVICE_GUARD(g->ctx);
     comap_ctx *ctx = g->ctx;
-    comap_destriper *d = g->d;
     if (const int rc = ground_dist_scratch(g)) return rc;
-    hipStream_t st = ctx->stream;
-    const int64_t NO = g->NO, K = g->K;
-    double *xp = g->dist;
-    k_gr_fold<<<grid_for(NO), 256, 0, st>>>(p, p + NO + K, g->gint, NO, xp, d->cf ? d->wbar : nullptr, d->pt, flags);
-    ds_launch_bin(d, st, d->cf ? d->pt : xp, nullptr, nullptr, num, flags, false, d->cf);
-    k_gr_bin<<<grid_for(g->npix * kBinLanes, 65536), 256, 0, st>>>(g->gprow, g->gpk, g->gpa, p + NO, 1.0, g->npix, num,
-                                                                   flags);
+    launch_fold_bin(g, ctx->stream, p, g->dist, num, flags);
     COMAP_LAUNCH_CHECK(ctx);
     return 0;
 }
@@ -1111,15 +1113,9 @@ extern "C" int comap_destripe_ground_dist_project(comap_ground *g, const double 
     if (!g || !p || !num || !h || !q || !scal || !flags) return -1;
     COMAP_DEVICE_GUARD(g->ctx);
     comap_ctx *ctx = g->ctx;
-    comap_destriper *d = g->d;
     if (!g->dist) return comap_fail(ctx, -1, "ground dist_project: call comap_destripe_ground_dist_bin on p first");
-    hipStream_t st = ctx->stream;
-    const int64_t NO = g->NO, K = g->K;
-    const double *xp = g->dist;
-    ds_launch_project(d, st, xp, num, h, q, flags);
-    launch_ground_project(g, st, xp, p + NO, num, h, q, q + NO, flags);
-    ds_dot_part(d, st, p, q, NO);   // not gated: it writes the partials only
-    k_gr_pq<<<1, 256, 0, st>>>(d->part, p, q, NO, K, scal, flags);
+    launch_project_dot(g, ctx->stream, p, g->dist, num, h, q, flags);
+    k_gr_pq<<<1, 256, 0, ctx->stream>>>(g->d->part, p, q, g->NO, g->K, scal, flags);
     COMAP_LAUNCH_CHECK(ctx);
     return 0;
 }

@@ -342,6 +342,7 @@ inline unsigned grid_for(int64_t n, int64_t cap = 4096) { return (unsigned)std::
 //   ds_dot             out = a . b over n values
 //   ds_dot_part        k_dot_part alone: kRedBlocks block partials of a . b in d->part
 //   ds_upd_grid        the CG update's grid (hence its r.r partials) for NO offsets
+//   ds_div_map         out_p = num_p / h_p (num_p where h_p == 0) over n values
 int ds_cg_state(comap_destriper *d);
 bool ds_cg_use_graph(const comap_destriper *d);
 void ds_launch_bin(const comap_destriper *d, hipStream_t st, const double *x, const double *base, const double *hdiv,
@@ -351,6 +352,7 @@ void ds_launch_project(const comap_destriper *d, hipStream_t st, const double *x
 void ds_dot(comap_destriper *d, hipStream_t st, const double *a, const double *b, int64_t n, double *out);
 void ds_dot_part(comap_destriper *d, hipStream_t st, const double *a, const double *b, int64_t n);
 unsigned ds_upd_grid(int64_t NO);
+void ds_div_map(hipStream_t st, const double *num, const double *h, int64_t n, double *out);
 
 // a problem's persistent buffers come from the cached device pool (comap_tmp_alloc) in
 // the context stream's order; comap_destripe_destroy returns them after a device sync

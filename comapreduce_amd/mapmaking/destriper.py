@@ -44,6 +44,19 @@ def torch_allreduce(t):
     return t
 
 
+def _device(device):
+    """torch's device object of HIP device ``device`` (None: the current one)."""
+    import torch
+    return torch.device('cuda', N.current_device() if device is None else int(device))
+
+
+def _to_tensor(a, dev, dt):
+    """Array or tensor as a tensor of dtype ``dt`` on ``dev``."""
+    import torch
+    t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
+    return t.to(device=dev, dtype=dt)
+
+
 class TimedAllreduce:
     """torch_allreduce with every call bracketed by HIP events on the current stream (the
     stream the CG kernels run on, which waits for the collective): the measured
@@ -145,12 +158,14 @@ def cg_solve(ops, allreduce, threshold=1e-6, niter=100, h=None, nnum=None):
 def cg_solve_batched(ops, allreduce, threshold=1e-6, niter=100, batch=16):
     """Multi-rank CG of the device path: the iterates of ``cg_solve`` (same
     order of operations and cross-rank sums), but with the convergence test on
-    the device (comap_destripe_dist_direction's stop flags) so ``batch``
-    iterations -- kernels and all-reduces -- are queued per host round trip.
-    Iterations queued after convergence are no-ops (their all-reduces sum
-    stale buffers that are not read again).  Works for every band of a batched
+    the device (the direction call's stop flags) so ``batch`` iterations --
+    kernels and all-reduces -- are queued per host round trip.  Iterations
+    queued after convergence are no-ops (their all-reduces sum stale buffers
+    that are not read again).  ``ops`` is a DeviceOps -- every band of a batched
     problem at once (vectors interleaved [n][nb], one all-reduce per sum for
-    all bands).  Returns (x in the problem's internal offset order -- see
+    all bands) -- or a GroundOps (nb = 1, vectors [x | s | c]; the iterates of
+    ``cg_solve`` bit for bit, as each rank holds whole (observation, feed)
+    groups).  Returns (x in the problem's internal offset order -- see
     DeviceOps.natural --, iterations per band (list), h, nnum)."""
     nb = ops.nb
     x, h, nnum, flags, iteration = _dist_start(ops, allreduce, threshold)
@@ -189,16 +204,15 @@ def _dist_start(ops, allreduce, threshold):
 
 
 def _dist_iteration(ops, allreduce, p, num, h, q, scal, flags, x, r):
-    """One multi-rank CG iteration as a no-argument callable: by default the native
-    solve's 4 kernels with the p.q / r.r block partials all-reduced
-    (comap_destripe_dist_*_parts / _fused); COMAP_DS_DIST_FUSED=0 (and operator
-    objects without them, e.g. the oracle's) use the 7-launch pieces that all-reduce
-    final sums."""
+    """One multi-rank CG iteration as a no-argument callable: 4 native calls cut at the three
+    all-reduces.  An operator with ``dist_parts`` (DeviceOps) runs the native solve's 4 kernels
+    and all-reduces the p.q / r.r block partials (comap_destripe_dist_*_parts / _fused); any
+    other (GroundOps) leaves its sums in scal, whose p.q and r.r are all-reduced."""
     nb = ops.nb
-    if hasattr(ops, 'dist_parts') and os.environ.get('COMAP_DS_DIST_FUSED', '1') != '0':
+    if hasattr(ops, 'dist_parts'):
         pq_part, rr_part = ops.dist_parts()
 
-        def fused():
+        def parts():
             ops.dist_bin(p, num, flags)
             allreduce(num)
             ops.dist_project_parts(p, num, h, q, pq_part, flags)
@@ -206,9 +220,9 @@ def _dist_iteration(ops, allreduce, p, num, h, q, scal, flags, x, r):
             ops.dist_update_fused(scal, pq_part, x, r, p, q, rr_part, flags)
             allreduce(rr_part)
             ops.dist_direction_fused(scal, rr_part, p, r, flags)
-        return fused
+        return parts
 
-    def pieces():
+    def sums():
         ops.dist_bin(p, num, flags)
         allreduce(num)
         ops.dist_project(p, num, h, q, scal, flags)
@@ -216,48 +230,7 @@ def _dist_iteration(ops, allreduce, p, num, h, q, scal, flags, x, r):
         ops.dist_update(scal, x, r, p, q, flags)
         allreduce(scal[3 * nb:4 * nb])
         ops.dist_direction(scal, p, r, flags)
-    return pieces
-
-
-def cg_solve_ground_batched(g, allreduce, threshold=1e-6, niter=100, batch=16):
-    """Multi-rank CG of the ground-template operator (``GroundOps``): the iterates of
-    ``cg_solve(g, allreduce)`` bit for bit -- the same launches, local summation orders and
-    cross-rank sums -- with the stop test on the device (comap_destripe_ground_dist_*), so
-    ``batch`` iterations are queued per host read of the flags: 4 native calls and 3
-    all-reduces (num, scal[2:3], scal[3:4]) per iteration instead of 11 calls, 3 all-reduces
-    and a blocking read of r.r.  Each rank holds whole (observation, feed) groups, so its
-    offsets, slopes and levels are rank-local; iterations queued after the stop are no-ops.
-    Returns (u = [x internal order | s | c], iterations, h, nnum) like ``cg_solve``."""
-    h0, _, n0 = g.local_maps()
-    h = allreduce(h0)
-    nnum = allreduce(n0)
-    n = g.n_offsets
-    x, r, q = g.zeros(n), g.zeros(n), g.zeros(n)
-    num = g.zeros(g.npix)
-    g.project(None, nnum, h, r)                  # b, ground tail included; r = p = b (u0 = 0)
-    p = g.copy(r)
-    scal = g.zeros(5)                            # rr0, rr, pq, rr_new, threshold
-    g.dot(r, r, scal[0:1])
-    allreduce(scal[0:1])
-    scal[1:2].copy_(scal[0:1])
-    scal[3:4].copy_(scal[0:1])
-    scal[4] = float(threshold)
-    flags = g.torch.zeros(4, dtype=g.torch.int32, device=g.dev)
-    enq = 0
-    while enq < niter:
-        k = min(batch, niter - enq)
-        for _ in range(k):
-            g.dist_bin(p, num, flags)
-            allreduce(num)
-            g.dist_project(p, num, h, q, scal, flags)
-            allreduce(scal[2:3])
-            g.dist_update(scal, x, r, p, q, flags)
-            allreduce(scal[3:4])
-            g.dist_direction(scal, p, r, flags)
-        enq += k
-        if int(flags[0].item()):
-            break
-    return x, int(flags[3].item()), h, nnum
+    return sums
 
 
 def cg_solve_graph(ops, allreduce, threshold=1e-6, niter=100, batch=16):
@@ -292,7 +265,26 @@ def cg_solve_graph(ops, allreduce, threshold=1e-6, niter=100, batch=16):
     return x, [int(v) for v in flags[2 + nb:2 + 2 * nb].tolist()], h, nnum
 
 
-class DeviceOps:
+class _Vectors:
+    """The vector helpers of cg_solve's protocol on float64 device tensors (self.torch, self.dev)."""
+
+    def zeros(self, n):
+        return self.torch.zeros(n, dtype=self.torch.float64, device=self.dev)
+
+    def scalar(self):
+        return self.zeros(1)
+
+    def copy(self, a):
+        return a.clone()
+
+    def host_scalar(self, s):
+        return float(s.item())
+
+    def set_scalar(self, dst, src):
+        dst.copy_(src)
+
+
+class DeviceOps(_Vectors):
     """One rank's destriper operator on the GPU (comap_destripe_* C ABI).
 
     ``tod``/``weights`` are [N] (one band) or [n_bands, N] (several sidebands on
@@ -307,9 +299,8 @@ class DeviceOps:
         pixel."""
         import torch
         self.torch = torch
-        device = N.current_device() if device is None else int(device)
-        self.dev = torch.device('cuda', device)
-        self.ctx = N.ctx(device)
+        self.dev = _device(device)
+        self.ctx = N.ctx(self.dev.index)
         self.pix = self._t(pixels, torch.int32)
         tod2 = self._t2(tod, torch.float64)
         w2 = self._t2(weights, torch.float64)
@@ -353,15 +344,10 @@ class DeviceOps:
         self.n_offsets = int(N.lib().comap_destripe_n_offsets(h))
 
     def _t(self, a, dt):
-        torch = self.torch
-        if isinstance(a, torch.Tensor):
-            return a.to(device=self.dev, dtype=dt).contiguous().reshape(-1)
-        return torch.from_numpy(np.ascontiguousarray(a)).to(device=self.dev, dtype=dt).reshape(-1)
+        return _to_tensor(a, self.dev, dt).contiguous().reshape(-1)
 
     def _t2(self, a, dt):
-        torch = self.torch
-        t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
-        t = t.to(device=self.dev, dtype=dt)
+        t = _to_tensor(a, self.dev, dt)
         return t.reshape(1, -1).contiguous() if t.dim() == 1 else t.contiguous()
 
     def natural(self, x):
@@ -402,21 +388,6 @@ class DeviceOps:
     def empty(self, n):
         """[n] float64 on the device, uninitialised (for outputs a call writes in full)."""
         return N.device_empty(n, self.torch.float64, self.dev)
-
-    def zeros(self, n):
-        return self.torch.zeros(n, dtype=self.torch.float64, device=self.dev)
-
-    def scalar(self):
-        return self.zeros(1)
-
-    def copy(self, a):
-        return a.clone()
-
-    def host_scalar(self, s):
-        return float(s.item())
-
-    def set_scalar(self, dst, src):
-        dst.copy_(src)
 
     def _c(self, fn, *args):
         N.bind_stream(self.ctx, self.dev)
@@ -468,23 +439,11 @@ class DeviceOps:
     def cg_direction(self, rr_new, rr, p, r):
         self._c('comap_destripe_cg_direction', self.h, self._s(rr_new), self._s(rr), self._v(p), self._v(r))
 
-    # ---- multi-rank iteration pieces (device stop flags; see cg_solve_batched)
+    # ---- multi-rank iteration pieces (device stop flags; see cg_solve_batched): the native
+    # solve's 4 launches, with the p.q / r.r block partials all-reduced between them
     def dist_bin(self, p, num, flags):
         self._c('comap_destripe_dist_bin', self.h, self._v(p), self._m(num), self._f(flags))
 
-    def dist_project(self, p, num, h, q, scal, flags):
-        self._c('comap_destripe_dist_project', self.h, self._v(p), self._m(num), self._m(h), self._v(q),
-                self._s(scal, 4 * self.nb + 1), self._f(flags))
-
-    def dist_update(self, scal, x, r, p, q, flags):
-        self._c('comap_destripe_dist_update', self.h, self._s(scal, 4 * self.nb + 1), self._v(x), self._v(r),
-                self._v(p), self._v(q), self._f(flags))
-
-    def dist_direction(self, scal, p, r, flags):
-        self._c('comap_destripe_dist_direction', self.h, self._s(scal, 4 * self.nb + 1), self._v(p), self._v(r),
-                self._f(flags))
-
-    # ---- the same iteration with block partials all-reduced (4 launches, as the native solve)
     def dist_parts(self):
         """Zeroed [nb * comap_destripe_dist_parts()] partial buffers for p.q and r.r."""
         n = int(N.lib().comap_destripe_dist_parts()) * self.nb
@@ -635,10 +594,11 @@ def _ranks_agree(d, error, held=None):
     merge_ground_tables([t for _, t in everyone])
 
 
-class GroundOps:
+class GroundOps(_Vectors):
     """The destriper operator with a ground (azimuth) template per (observation, feed):
     the reference's op_Ax_with_ground (Destriper.py:265-336) as the operator object that
-    ``cg_solve`` drives (comap_destripe_ground_* around a DeviceOps' own calls).
+    ``cg_solve`` and ``cg_solve_batched`` drive (comap_destripe_ground_* around a DeviceOps' own
+    calls).
 
     Vectors hold [x (N/L offsets, internal order) | s (K slopes) | c (K levels)], groups in
     ``ground_groups`` order.  The azimuth enters centred and scaled per group, a = (az -
@@ -650,7 +610,7 @@ class GroundOps:
         torch = ops.torch
         if ops.nb != 1:
             raise NotImplementedError('the ground template solves one band (batched bands are not supported)')
-        self.ops, self.torch, self.dev, self.ctx = ops, torch, ops.dev, ops.ctx
+        self.ops, self.torch, self.dev, self.ctx, self.nb = ops, torch, ops.dev, ops.ctx, 1
         self.K, self.NO, self.npix = int(n_groups), ops.n_offsets, ops.npix
         self.n_offsets = self.NO + 2 * self.K
         az = ops._t(az, torch.float64)
@@ -692,22 +652,6 @@ class GroundOps:
         a, b = ctypes.c_int64(), ctypes.c_int64()
         N.lib().comap_destripe_ground_nnz(self.g, ctypes.byref(a), ctypes.byref(b))
         return int(a.value), int(b.value)
-
-    # ---- vector helpers (cg_solve's protocol)
-    def zeros(self, n):
-        return self.ops.zeros(n)
-
-    def scalar(self):
-        return self.ops.zeros(1)
-
-    def copy(self, a):
-        return a.clone()
-
-    def host_scalar(self, s):
-        return float(s.item())
-
-    def set_scalar(self, dst, src):
-        dst.copy_(src)
 
     def local_maps(self):
         return self.ops.local_maps()
@@ -774,7 +718,7 @@ class GroundOps:
         self._c('comap_destripe_ground_tail_direction', self.g, self.ops._s(rr_new), self.ops._s(rr), self._tail(p),
                 self._tail(r))
 
-    # ---- multi-rank iteration pieces (device stop flags; see cg_solve_ground_batched)
+    # ---- multi-rank iteration pieces (device stop flags; see cg_solve_batched)
     def dist_bin(self, p, num, flags):
         self._folded = None
         self._c('comap_destripe_ground_dist_bin', self.g, N.dptr(self._u(p)), self.ops._m(num), self.ops._f(flags))
@@ -836,7 +780,7 @@ def copy_stream(dev):
 
 
 # The ground solve's driver across ranks when COMAP_DS_GROUND_SOLVE is not set: 'batched'
-# (cg_solve_ground_batched) or 'eager' (cg_solve).  Eager until the batched driver measures
+# (cg_solve_batched) or 'eager' (cg_solve).  Eager until the batched driver measures
 # faster outside the rounds' spread: with two gloo ranks on one GPU it did at one observation per
 # rank and did not at four; no multi-GPU figure exists yet.
 GROUND_RANKS_SOLVE = 'eager'
@@ -991,8 +935,7 @@ class DeviceDestriper:
         nmax = max(self.counts)
 
         def as_t(a, dt):
-            t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
-            return t.to(device=cdev, dtype=dt)
+            return _to_tensor(a, cdev, dt)
 
         def gather(t, width):       # t [rows, n_local] -> root: list of [rows, width]
             pad = torch.zeros((t.shape[0], width), dtype=t.dtype, device=cdev)
@@ -1012,7 +955,7 @@ class DeviceDestriper:
             self.ops = None
             self._ref = (device, nbands)
             return
-        dev = torch.device('cuda', N.current_device() if device is None else int(device))
+        dev = _device(device)
         cat = lambda parts, per: torch.cat([parts[r][:, :c // per] for r, c in enumerate(self.counts)], dim=1).to(dev)  # noqa: E731
         p_all, t_all, w_all = cat(pix, 1).reshape(-1), cat(td, 1), cat(wd, 1)
         k_all = cat(kp, L) if kp is not None else None
@@ -1030,7 +973,7 @@ class DeviceDestriper:
         nb = 4 if nbands == 3 else nbands
         L, counts = self.gathered['L'], self.gathered['counts']
         npix = self.npix_full
-        dev = torch.device('cuda', N.current_device() if device is None else int(device))
+        dev = _device(device)
         nomax = max(counts) // L
         keys = ('map', 'naive', 'weight', 'hits')
         if rank == 0:
@@ -1065,9 +1008,8 @@ class DeviceDestriper:
         offsets crossing one pixel then sit close together, which is what the CG bin's x
         gathers touch."""
         import torch
-        dev = torch.device('cuda', N.current_device() if device is None else int(device))
-        pix = pixels.to(device=dev, dtype=torch.int32).reshape(-1) if isinstance(pixels, torch.Tensor) else \
-            torch.from_numpy(np.ascontiguousarray(pixels, dtype=np.int32)).to(dev).reshape(-1)
+        dev = _device(device)
+        pix = _to_tensor(pixels, dev, torch.int32).reshape(-1)
         ids, nt = tiled_layout(ny, nx, T, dev)
         # one device pass (comap_relabel_pixels), no host sync: an id outside [-npix, npix)
         # becomes nt, which the set-up's device range check rejects (IndexError), as it
@@ -1102,9 +1044,7 @@ class DeviceDestriper:
         offsets' spatial order and hence every iterate are unchanged, bit for bit.  Maps are
         expanded back to npix in solve()."""
         import torch
-        dev = torch.device('cuda', N.current_device() if device is None else int(device))
-        pix = pixels.to(device=dev, dtype=torch.int64).reshape(-1) if isinstance(pixels, torch.Tensor) else \
-            torch.from_numpy(np.ascontiguousarray(pixels, dtype=np.int64)).to(dev).reshape(-1)
+        pix = _to_tensor(pixels, _device(device), torch.int64).reshape(-1)
         if pix.numel() and (int(pix.max().item()) >= npix or int(pix.min().item()) < -npix):
             raise IndexError(f'pixel index out of range for a map of {npix} pixels (valid: -{npix} .. {npix - 1})')
         comp, self.hit_index = compact_pixels(pix, npix, torch_allreduce)
@@ -1156,7 +1096,8 @@ class DeviceDestriper:
             split = ops.split_bands
         else:
             # COMAP_DS_GRAPH=1: the captured-graph driver (one launch per 16 iterations);
-            # default: the eager batched driver (7 host calls per iteration, 16 per check)
+            # default: the eager batched driver (4 native calls and 3 all-reduces per iteration,
+            # 16 iterations per check)
             # (graph capture of a collective needs RCCL: with any other backend, e.g. the gloo
             # rehearsals, the eager driver runs instead)
             solver = cg_solve_batched
@@ -1168,18 +1109,9 @@ class DeviceDestriper:
                     warnings.warn(f'COMAP_DS_GRAPH=1 needs the nccl (RCCL) backend, not {d.get_backend()}: '
                                   'using the eager CG driver')
             x, it, h, nnum = solver(ops, allreduce or torch_allreduce, threshold, niter)
-            _, hits, _ = ops.local_maps()
-            torch_allreduce(hits)
-            num = ops.zeros(ops.npix * ops.nb)
-            ops.bin(x, 1, num)
-            torch_allreduce(num)
-            maps = {'map': ops.zeros(ops.npix * ops.nb), 'naive': ops.zeros(ops.npix * ops.nb), 'weight': h,
-                    'hits': hits}
-            ops.div_map(num, h, maps['map'])
-            ops.div_map(nnum, h, maps['naive'])
+            maps = self._finish_maps(ops, x, h, nnum)
             it = it[:ops.n_bands]
             x = ops.natural(x)
-            maps = {k: self._expand(v) for k, v in maps.items()}
             split = ops.split_bands
         if self.layout is not None:
             nbl = nb if self.gathered is not None else ops.nb
@@ -1191,81 +1123,68 @@ class DeviceDestriper:
         maps['map2'] = maps['weight']
         return {'x': split(x), 'iters': it, 'maps': maps}
 
+    def _finish_maps(self, op, u, h, nnum):
+        """The device maps {'map', 'naive', 'weight', 'hits'} of solution ``u`` of operator ``op``
+        (self.ops or self.gops: op.bin(u, 1, num) is the rank's naive numerator - W u), from the
+        global weight map h and naive numerator nnum: hits and the numerator summed across
+        ranks, divided by h and expanded to the full map."""
+        ops = self.ops
+        n = ops.npix * ops.nb
+        _, hits, _ = ops.local_maps()
+        torch_allreduce(hits)
+        num = ops.zeros(n)
+        op.bin(u, 1, num)
+        torch_allreduce(num)
+        maps = {'map': ops.zeros(n), 'naive': ops.zeros(n), 'weight': h, 'hits': hits}
+        ops.div_map(num, h, maps['map'])
+        ops.div_map(nnum, h, maps['naive'])
+        return {k: self._expand(v) for k, v in maps.items()}
 
     def _solve_ground(self, threshold, niter, to_host):
-        """solve() with the ground template: the native device-resident CG on GroundOps
-        (``GroundOps.solve_native``; COMAP_DS_GROUND_SOLVE=eager, read here: the eager
-        ``cg_solve`` driver, the comparison baseline), then the maps from the offsets AND the
-        fitted templates.  Adds 'ground': {'obsids', 'feeds', 'slope', 'level', 'wrapped'} (host
-        arrays [n_obs, n_feeds], GroundOps.fit's units; 'wrapped': the group crosses azimuth
-        0 / 360 and was fitted on az + 360 where az < 180); 'x' holds the offsets."""
+        """solve() with the ground template, then the maps from the offsets AND the fitted
+        templates.  COMAP_DS_GROUND_SOLVE, read here, picks the CG: on one rank 'native' (the
+        default: ``GroundOps.solve_native``, device-resident) or 'eager' (Python's ``cg_solve``,
+        the comparison baseline); across ranks (sharded, on the rank's own groups) 'eager' with
+        the sharded all-reduces (the default, GROUND_RANKS_SOLVE) or 'batched' (= 'native':
+        ``cg_solve_batched``, device stop test, 16 iterations per host check; the same iterates
+        bit for bit), the maps then from the all-reduced numerator, hits and global weight map.
+        Adds 'ground': {'obsids', 'feeds', 'slope', 'level', 'wrapped'} (host arrays [n_obs,
+        n_feeds], GroundOps.fit's units; 'wrapped': the group crosses azimuth 0 / 360 and was
+        fitted on az + 360 where az < 180): across ranks the merged table on rank 0, None
+        elsewhere.  'x' holds the rank's offsets, 'solution' its whole CG vector [x internal
+        order | s | c] in GroundOps' units."""
         ops, g = self.ops, self.gops
         d = _dist()
-        if d is not None and d.get_world_size() > 1:
-            return self._solve_ground_ranks(d, threshold, niter, to_host)
-        mode = os.environ.get('COMAP_DS_GROUND_SOLVE', 'native')
+        ranks = d is not None and d.get_world_size() > 1
+        mode = os.environ.get('COMAP_DS_GROUND_SOLVE', GROUND_RANKS_SOLVE if ranks else 'native')
         if mode == 'eager':
-            u, it, h, nnum = cg_solve(g, lambda t: t, threshold, niter)
-            _, hits, _ = ops.local_maps()
-            num = ops.zeros(ops.npix)
-            g.bin(u, 1, num)
-            maps = {'map': ops.zeros(ops.npix), 'naive': ops.zeros(ops.npix), 'weight': h, 'hits': hits}
-            ops.div_map(num, h, maps['map'])
-            ops.div_map(nnum, h, maps['naive'])
+            u, it, h, nnum = cg_solve(g, torch_allreduce, threshold, niter)
+        elif ranks and mode in ('batched', 'native'):
+            u, its, h, nnum = cg_solve_batched(g, torch_allreduce, threshold, niter)
+            it = its[0]
         elif mode == 'native':
             u, it, maps = g.solve_native(threshold, niter)
         else:
-            raise ValueError(f"COMAP_DS_GROUND_SOLVE must be 'native' or 'eager', not {mode!r}")
+            raise ValueError("COMAP_DS_GROUND_SOLVE must be 'native', 'eager' or, across ranks, 'batched', "
+                             f'not {mode!r}')
+        if ranks or mode == 'eager':
+            maps = self._finish_maps(g, u, h, nnum)
         if self.layout is not None:
             maps = {k: self._untile(v, 1) for k, v in maps.items()}
         maps['map2'] = maps['weight']
         uobs, ufeed = self.ground
         slope, level = (v.cpu().numpy().reshape(uobs.size, ufeed.size) for v in g.fit(u))
-        wrapped = g.wrapped.cpu().numpy().reshape(uobs.size, ufeed.size) != 0
-        # ('solution': the whole CG vector [x internal order | s | c], GroundOps' units)
-        return {'x': ops.natural(u), 'iters': it, 'maps': maps_to_host(maps) if to_host else maps,
-                'ground': {'obsids': uobs, 'feeds': ufeed, 'slope': slope, 'level': level, 'wrapped': wrapped},
-                'solution': u}
-
-
-    def _solve_ground_ranks(self, d, threshold, niter, to_host):
-        """_solve_ground across ranks (sharded), on the rank's own groups: the eager
-        ``cg_solve`` with the sharded all-reduces (the default, GROUND_RANKS_SOLVE) or, with
-        COMAP_DS_GROUND_SOLVE=batched, ``cg_solve_ground_batched`` (device stop test, 16
-        iterations per host check; the same iterates bit for bit); the maps from the
-        all-reduced numerator, hits and the global weight map.  'x' and 'solution' stay
-        rank-local; 'ground' is the merged table on rank 0, None elsewhere."""
-        ops, g = self.ops, self.gops
-        mode = os.environ.get('COMAP_DS_GROUND_SOLVE', GROUND_RANKS_SOLVE)
-        if mode == 'eager':
-            u, it, h, nnum = cg_solve(g, torch_allreduce, threshold, niter)
-        elif mode in ('batched', 'native'):
-            u, it, h, nnum = cg_solve_ground_batched(g, torch_allreduce, threshold, niter)
-        else:
-            raise ValueError(f"COMAP_DS_GROUND_SOLVE must be 'batched' (or 'native') or 'eager', not {mode!r}")
-        _, hits, _ = ops.local_maps()
-        torch_allreduce(hits)
-        num = ops.zeros(ops.npix)
-        g.bin(u, 1, num)                 # the rank's naive numerator - W x' - ground bin(s)
-        torch_allreduce(num)
-        maps = {'map': ops.zeros(ops.npix), 'naive': ops.zeros(ops.npix), 'weight': h, 'hits': hits}
-        ops.div_map(num, h, maps['map'])
-        ops.div_map(nnum, h, maps['naive'])
-        maps = {k: self._expand(v) for k, v in maps.items()}
-        if self.layout is not None:
-            maps = {k: self._untile(v, 1) for k, v in maps.items()}
-        maps['map2'] = maps['weight']
-        uobs, ufeed = self.ground
-        slope, level = (v.cpu().numpy().reshape(uobs.size, ufeed.size) for v in g.fit(u))
-        wrapped = g.wrapped.cpu().numpy().reshape(uobs.size, ufeed.size) != 0
-        tables = [None] * d.get_world_size()
-        d.all_gather_object(tables, {'obsids': uobs, 'feeds': ufeed, 'slope': slope, 'level': level,
-                                     'wrapped': wrapped, 'held': self.held})
-        rank = d.get_rank()
+        table = {'obsids': uobs, 'feeds': ufeed, 'slope': slope, 'level': level,
+                 'wrapped': g.wrapped.cpu().numpy().reshape(uobs.size, ufeed.size) != 0}
+        rank = 0
+        if ranks:
+            tables = [None] * d.get_world_size()
+            d.all_gather_object(tables, dict(table, held=self.held))
+            rank = d.get_rank()
+            table = merge_ground_tables(tables) if rank == 0 else None
         if to_host:
             maps = maps_to_host(maps) if rank == 0 else None
-        return {'x': ops.natural(u), 'iters': it, 'maps': maps,
-                'ground': merge_ground_tables(tables) if rank == 0 else None, 'solution': u}
+        return {'x': ops.natural(u), 'iters': it, 'maps': maps, 'ground': table, 'solution': u}
 
 
 def maps_to_host(maps):
@@ -1304,24 +1223,16 @@ def run_destriper(_pointing, _tod, _weights, offset_length, pixel_edges, az=None
     if device is None:
         device = torch.cuda.current_device()
     npix = int(pixel_edges[-1]) + 1
-    if ground:
-        if az is None or feedid is None or obsids is None:
-            raise ValueError('ground=True needs az, feedid and obsids')
-        dd = DeviceDestriper(np.asarray(_pointing), np.asarray(_tod, dtype=np.float64),
-                             np.asarray(_weights, dtype=np.float64), int(offset_length), npix, device,
-                             map_shape=map_shape, ground=(np.asarray(az, dtype=np.float64), feedid, obsids))
-        res = dd.solve(threshold, niter, to_host=True)
-        if res['maps'] is None:          # a rank other than 0
-            return {'All': {'map': None, 'naive': None, 'weight': None, 'map2': None}, 'Ground': None}
-        return {'All': res['maps'], 'Ground': res['ground']}
+    if ground and (az is None or feedid is None or obsids is None):
+        raise ValueError('ground=True needs az, feedid and obsids')
     dd = DeviceDestriper(np.asarray(_pointing), np.asarray(_tod, dtype=np.float64),
-                         np.asarray(_weights, dtype=np.float64), int(offset_length), npix, device, map_shape=map_shape)
+                         np.asarray(_weights, dtype=np.float64), int(offset_length), npix, device, map_shape=map_shape,
+                         ground=(np.asarray(az, dtype=np.float64), feedid, obsids) if ground else None)
     res = dd.solve(threshold, niter, to_host=True)
-    d = _dist()
-    rank = d.get_rank() if d is not None else 0
-    if rank != 0:
-        return {'All': {'map': None, 'naive': None, 'weight': None, 'map2': None}}
-    return {'All': res['maps']}
+    maps = res['maps']
+    if maps is None:                     # a rank other than 0
+        maps = {'map': None, 'naive': None, 'weight': None, 'map2': None}
+    return {'All': maps, 'Ground': res['ground']} if ground else {'All': maps}
 
 
 def run_destriper_bands(_pointing, _tods, _weights, offset_length, pixel_edges, keep=None, threshold=1e-6,

@@ -284,36 +284,27 @@ int comap_destripe_cg_update(comap_destriper *d, const double *rr_dev, const dou
 int comap_destripe_cg_direction(comap_destriper *d, const double *rr_new_dev, const double *rr_dev,
                                 double *p_dev, const double *r_dev);
 /* Multi-rank CG iteration (Destriper.py:85-152 with p == pb), split at the
- * three cross-rank sums the caller performs between the calls (NB = bands):
- *   dist_bin        num = W p (local numerator)          -> all-reduce num
- *   dist_project    q = F^T W (F p - m[p]), m = num/h;
- *                   pq = local q.p                        -> all-reduce pq
- *   dist_update     alpha = rr/pq; x += alpha p; r -= alpha q;
- *                   rr_new = local r.r                    -> all-reduce rr_new
- *   dist_direction  p = r + (rr_new/rr) p; rr = rr_new; per band: count the
- *                   iteration, stop when rr_new/rr0 is NaN or below threshold.
- * scal_dev f64 [4 NB + 1], k-major: rr0[NB], rr[NB], pq[NB], rr_new[NB],
- * threshold; flags_dev int32 [2 + 2 NB]: all bands stopped, iterations any band
- * ran, stopped[NB], iterations[NB].  A stopped band is left unchanged and every
- * kernel returns at once when flags[0] is set, so a batch of iterations can be
- * queued with one host check of flags per batch (NB = 1: rr0, rr, pq, rr_new,
- * threshold / stop, iterations). */
+ * three cross-rank sums the caller performs between the calls (NB = bands); the
+ * native solve's 4 kernels, with the block PARTIALS of p.q and r.r all-reduced
+ * instead of their sums, so no final-sum launches:
+ *   dist_bin             num = W p (local numerator)            -> all-reduce num
+ *   dist_project_parts   q = F^T W (F p - m[p]), m = num/h;
+ *                        p.q partials                           -> all-reduce pq_part
+ *   dist_update_fused    pq = sum(pq_part); alpha = rr/pq; x += alpha p;
+ *                        r -= alpha q; r.r partials             -> all-reduce rr_part
+ *   dist_direction_fused rr_new = sum(rr_part); p = r + (rr_new/rr) p; per band:
+ *                        count the iteration, stop when rr_new/rr0 is NaN or
+ *                        below threshold.
+ * scal_dev f64 [4 NB + 1], k-major: rr0[NB], rr[NB], pq[NB], rr_new[NB] (initialised
+ * to rr0, the current r.r), threshold; flags_dev int32 [2 + 2 NB]: all bands stopped,
+ * iterations any band ran, stopped[NB], iterations[NB].  A stopped band is left
+ * unchanged and every kernel returns at once when flags[0] is set, so a batch of
+ * iterations can be queued with one host check of flags per batch (NB = 1: rr0, rr,
+ * pq, rr_new, threshold / stop, iterations).  pq_part_dev / rr_part_dev f64
+ * [NB][comap_destripe_dist_parts()], zeroed by the caller before the first iteration
+ * (a rank writes its own blocks' slots; every rank re-sums all slots in one fixed
+ * order, so the scalars agree across ranks). */
 int comap_destripe_dist_bin(comap_destriper *d, const double *p_dev, double *num_dev, const int32_t *flags_dev);
-int comap_destripe_dist_project(comap_destriper *d, const double *p_dev, const double *num_dev,
-                                const double *h_dev, double *q_dev, double *scal_dev, const int32_t *flags_dev);
-int comap_destripe_dist_update(comap_destriper *d, double *scal_dev, double *x_dev, double *r_dev,
-                               const double *p_dev, const double *q_dev, const int32_t *flags_dev);
-int comap_destripe_dist_direction(comap_destriper *d, double *scal_dev, double *p_dev, const double *r_dev,
-                                  int32_t *flags_dev);
-/* The same iteration with the block PARTIALS of p.q and r.r all-reduced instead of
- * their sums, so no final-sum launches: the native solve's 4 kernels per iteration.
- * pq_part_dev / rr_part_dev f64 [NB][comap_destripe_dist_parts()], zeroed by the
- * caller before the first iteration (a rank writes its own blocks' slots; every rank
- * re-sums all slots in one fixed order, so the scalars agree across ranks).  scal as
- * above, with rr_new[NB] initialised to rr0 (the current r.r):
- *   dist_project_parts   q = F^T W (F p - m[p]); p.q partials -> all-reduce pq_part
- *   dist_update_fused    pq = sum(pq_part); x, r; r.r partials -> all-reduce rr_part
- *   dist_direction_fused rr_new = sum(rr_part); p = r + (rr_new/rr) p; stop test */
 int32_t comap_destripe_dist_parts(void);
 int comap_destripe_dist_project_parts(comap_destriper *d, const double *p_dev, const double *num_dev,
                                       const double *h_dev, double *q_dev, double *pq_part_dev,
@@ -435,8 +426,8 @@ int comap_destripe_ground_tail_direction(comap_ground *g, const double *rr_new_d
 int comap_destripe_ground_solve(comap_ground *g, double threshold, int32_t niter, double *u_dev, double *map_dev,
                                 double *naive_dev, double *weight_dev, double *hits_dev, int32_t *iters_out);
 /* The ground solve's iteration split at the three cross-rank sums the caller performs between the
- * calls: the ground counterparts of comap_destripe_dist_bin / _project / _update / _direction, for
- * ranks that each hold whole (observation, feed) groups (slopes, levels and offsets are then
+ * calls (the plain problem's comap_destripe_dist_* all-reduce block partials; these all-reduce the
+ * two scalars), for ranks that each hold whole (observation, feed) groups (slopes, levels and offsets are then
  * rank-local unknowns; only the map numerator and the two CG scalars cross ranks).  Vectors are the
  * caller's, whole: f64 [N/L + 2K] = x (internal offset order) | s | c.  scal_dev f64 [5]: rr0, rr,
  * pq, rr_new, threshold, with rr and rr_new initialised to rr0; flags_dev int32 [4]: stop,

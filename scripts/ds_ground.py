@@ -25,7 +25,7 @@ reported as such, not measured).  The sharded ground solve's two drivers on the 
 alternated over ``rounds`` with early exit off, a barrier and a host clock around each solve that
 ends in a device synchronise (median reported, every rank's rounds kept):
 
-* ground_batched -- cg_solve_ground_batched (comap_destripe_ground_dist_*: 4 native calls and
+* ground_batched -- cg_solve_batched on GroundOps (comap_destripe_ground_dist_*: 4 native calls and
   3 all-reduces per iteration, one host read of the flags per 16);
 * ground_eager   -- cg_solve on GroundOps with the same all-reduces (11 calls, 3 all-reduces and
   a blocking read of r.r per iteration).
@@ -140,7 +140,7 @@ def _ranks_worker(rank, world, port, backend, obs, niter, rounds, q):
             tod, w, pix, az, feedid, obsids = c4_inputs(n_obs, 0, first=21 + rank * n_obs)
             dd = D.DeviceDestriper(pix, tod, w, 50, 480 * 480, 0, map_shape=(480, 480), ground=(az, feedid, obsids))
             g = dd.gops
-            drivers = {'ground_batched': lambda: D.cg_solve_ground_batched(g, D.torch_allreduce, 0.0, niter)[1],
+            drivers = {'ground_batched': lambda: D.cg_solve_batched(g, D.torch_allreduce, 0.0, niter)[1][0],
                        'ground_eager': lambda: D.cg_solve(g, D.torch_allreduce, 0.0, niter)[1]}
             for fn in drivers.values():
                 fn()

@@ -117,6 +117,25 @@ def test_stop_flag_freezes_the_state(problems):
     assert solve(dd, 'native', 1e-6, count - 1)['iters'] == count - 1
 
 
+# ---------------------------------------------------------------- 3b. the batched driver, one rank
+@pytest.mark.parametrize('which', ['a', 'b', 'c'])
+def test_batched_driver_equals_eager_on_one_rank(which, problems):
+    """cg_solve_batched on GroundOps (nb = 1; the driver the ranks use, here without ranks)
+    against cg_solve: the same iterates bit for bit.  16 and 17 iterations straddle the
+    16-iteration host check."""
+    from comapreduce_amd.mapmaking.destriper import cg_solve, cg_solve_batched
+    _, dd = problems(which)
+    g = dd.gops
+    assert (g.K, dd.ops.n_offsets) == {'a': (6, 115), 'b': (4, 1200), 'c': (300, 900)}[which]
+    for threshold, niter in ((0.0, 1), (0.0, 16), (0.0, 17), (1e-10, 1000)):
+        ub, itb, _, _ = cg_solve_batched(g, lambda t: t, threshold, niter)
+        ue, ite, _, _ = cg_solve(g, lambda t: t, threshold, niter)
+        print(f'case {which} threshold {threshold:g} niter {niter}: batched {itb}, eager {ite} iterations')
+        assert itb == [ite]
+        assert ite == niter if threshold == 0.0 else 1 < ite < 1000
+        assert np.array_equal(host(ub), host(ue))
+
+
 # ---------------------------------------------------------------- 4. determinism
 def test_native_solve_is_deterministic_with_and_without_the_graph():
     case = G.make_case(**CASES['b'])

@@ -1,6 +1,6 @@
 """The ground (azimuth) template across ranks: DeviceDestriper(ground=...) sharded over 2 gloo
 ranks that share cuda:0, each holding whole (observation, feed) groups -- the batched driver
-(cg_solve_ground_batched on comap_destripe_ground_dist_*) against the eager cg_solve on the same
+(cg_solve_batched on GroundOps' comap_destripe_ground_dist_*) against the eager cg_solve on the same
 ranks (bit for bit), against the dense NumPy solution and against the single-rank solve of the
 unsplit case, the merged res['ground'] table, errors that must arrive on every rank, and
 run_destriper.main(ground=True) under ranks.
