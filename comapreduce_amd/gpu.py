@@ -367,7 +367,14 @@ class GPUObservation:
         """Internal arrays (host f64): 0 rms [U,4,1024]; 1 mf [F,4,T]; 2 dG [F,T]; 3 x [U,4,1024,2] (valid
         only for pairs with needc); 4 mb; 5 kappa [3,U,4,1024]; 6 pass-D sums [U,4,16]; 7 alpha [U,4,1024];
         8 atmosphere (o, a) [U,4,1024,2]; 9 per (unit, band): channel-list length, median band on [U,4,2];
-        10 needc [U,4]: the pair took pass C and the per-channel regression solve."""
+        10 needc [U,4]: the pair took pass C and the per-channel regression solve.
+
+        Array 0 is the normalisation rms as normalise_data returns it (Level1Averaging.py:667-679):
+        nanstd of the stride-4 differences / sqrt 2 times sqrt(dnu tau), dnu = 2 GHz / 1024,
+        tau = 1 / 50 s (k_coef_b stores it with that factor); NaN where the unit has no fit for the
+        channel.  Array 7 is its reciprocal on the median channels (0 elsewhere, and where the
+        reciprocal is not finite).  Arrays 1, 2 and 4 are defined on the units' samples only
+        (1 and 4 only where array 9 says the median band is on).  Valid after average()."""
         U = self.units.shape[0]
         shapes = {0: (U, 4, 1024), 1: (self.F, 4, self.T), 2: (self.F, self.T), 3: (U, 4, 1024, 2),
                   4: (self.F, 4, self.T), 5: (3, U, 4, 1024), 6: (U, 4, 16), 7: (U, 4, 1024), 8: (U, 4, 1024, 2),

@@ -212,8 +212,11 @@ def median_index():
     return idx[(idx < 512 - 5) | (idx > 512 + 5)]
 
 
-def median_filter(tod, w=MEDFILT_WINDOW):
-    """Level1AveragingGainCorrection.median_filter, Level1Averaging.py:681-708."""
+def median_filter(tod, w=MEDFILT_WINDOW, means=None):
+    """Level1AveragingGainCorrection.median_filter, Level1Averaging.py:681-708.
+
+    ``means`` (an optional [B, n] array) receives the channel nanmean of every band,
+    the skipped ones included (for kernel-level checks)."""
     B, C, n = tod.shape
     out = np.zeros((B, C, n))
     idx = median_index()
@@ -223,6 +226,8 @@ def median_filter(tod, w=MEDFILT_WINDOW):
         with warnings.catch_warnings():
             warnings.simplefilter('ignore', RuntimeWarning)
             mean = np.nanmean(masked, axis=0)
+        if means is not None:
+            means[b] = mean
         if np.nansum(np.isfinite(mean)) < w * 2:
             continue
         pad = np.zeros(3 * n)
@@ -335,11 +340,14 @@ def reduce_scan(tod_scan, A_scan, fit, tsys, gain, source='', is_first_scan=Fals
     tod_scan f32[4,1024,n] (a copy; fill is applied to it), A_scan [n],
     fit [4,2,1024], tsys/gain [4,1024] (vane event 0).
     Returns (residual_avg [4,n], tod_original [4,n], weights [4]) and a dict of
-    intermediates for kernel-level checks."""
+    intermediates for kernel-level checks: 'nf' the normalisation rms [4,1024,1], 'mean'
+    the band means the median filter is run on [4,n] (every band), 'mf' their median
+    filter [4,n] (NaN rows: the band was skipped), 'dG' [n] or None."""
     tod_scan = fill_bad_data(tod_scan)
     clean = remove_atmosphere(A_scan, tod_scan, fit, source)
     clean, nf = normalise_data(clean)
-    clean, mf = median_filter(clean)
+    mean = np.full((clean.shape[0], clean.shape[-1]), np.nan)
+    clean, mf = median_filter(clean, means=mean)
     dG = None
     if power_spectrum_gate(clean[0]) and source not in CALIBRATORS:
         try:
@@ -363,13 +371,15 @@ def reduce_scan(tod_scan, A_scan, fit, tsys, gain, source='', is_first_scan=Fals
     with np.errstate(invalid='ignore'):
         orig = weighted_average_over_band(clean * tsys[:, :, None], wts)
     weights = 1.0 / auto_rms_rows(res) ** 2
-    return res, orig, weights, {'nf': nf, 'mf': mf, 'dG': dG}
+    return res, orig, weights, {'nf': nf, 'mean': mean, 'mf': mf, 'dG': dG}
 
 
-def average_tod(tod, A, edges, fit_values, tsys0, gain0, feeds, source=''):
+def average_tod(tod, A, edges, fit_values, tsys0, gain0, feeds, source='', keep=None):
     """Level1AveragingGainCorrection.average_tod, Level1Averaging.py:792-872.
 
-    tod f32[F,4,1024,T]; fit_values [S,F,4,2,1024]; tsys0/gain0 [F,4,1024]."""
+    tod f32[F,4,1024,T]; fit_values [S,F,4,2,1024]; tsys0/gain0 [F,4,1024].
+    ``keep`` (an optional dict) receives reduce_scan's intermediates per (feed index,
+    scan index)."""
     F, B, C, T = tod.shape
     out_tod = np.zeros((F, 4, T))
     out_orig = np.zeros((F, 4, T))
@@ -379,8 +389,10 @@ def average_tod(tod, A, edges, fit_values, tsys0, gain0, feeds, source=''):
             continue
         feed_tod = np.array(tod[f])          # h5py-like fresh copy per feed
         for i, (s, e) in enumerate(edges):
-            r, o, w, _ = reduce_scan(feed_tod[..., s:e].copy(), A[f, s:e], fit_values[i, f],
-                                     tsys0[f], gain0[f], source, is_first_scan=(i == 0))
+            r, o, w, info = reduce_scan(feed_tod[..., s:e].copy(), A[f, s:e], fit_values[i, f],
+                                        tsys0[f], gain0[f], source, is_first_scan=(i == 0))
+            if keep is not None:
+                keep[(f, i)] = info
             out_tod[f, :, s:e] = r
             out_orig[f, :, s:e] = o
             out_w[f, :, s:e] = w[:, None]
@@ -398,9 +410,9 @@ def scan_edges_calibrator(feats):
     return np.array([[int(min(idx))], [int(max(idx))]]).T
 
 
-def reduce_level1(data, source=''):
+def reduce_level1(data, source='', keep=None):
     """Full MeasureSystemTemperature -> AtmosphereRemoval ->
-    Level1AveragingGainCorrection on a dict of Level-1 datasets."""
+    Level1AveragingGainCorrection on a dict of Level-1 datasets (``keep``: see average_tod)."""
     d = data
     feats = features(d['spectrometer/features'])
     if source in CALIBRATORS:
@@ -413,7 +425,7 @@ def reduce_level1(data, source=''):
     tsys, gain = measure_system_temperature(tod, d['spectrometer/band_average'], feats, t_hot)
     A = airmass(d['spectrometer/pixel_pointing/pixel_el'])
     fit = filter_atmosphere(tod, A, edges, feats)
-    out = average_tod(tod, A, edges, fit, tsys[0], gain[0], d['spectrometer/feeds'], source)
+    out = average_tod(tod, A, edges, fit, tsys[0], gain[0], d['spectrometer/feeds'], source, keep)
     out['vane/system_temperature'] = tsys
     out['vane/system_gain'] = gain
     out['atmosphere/fit_values'] = fit
