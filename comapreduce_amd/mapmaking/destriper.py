@@ -470,6 +470,40 @@ class DeviceOps(_Vectors):
     def div_map(self, num, h, out):
         self._c('comap_destripe_div_map', self.h, self._m(num), self._m(h), self._m(out))
 
+    # ---- split maps (per-label maps of a solved problem, comap_destripe_split_maps)
+    def split_maps(self, x, labels, n_labels):
+        """The raw sums (num, naive_num, weight, hits), each [n_labels * npix * nb] (label, pixel,
+        band fastest), of this rank's samples per label: ``labels`` int32 CUDA [N/L] in
+        [-1, n_labels), ``x`` [N/L * nb] in the CALLER's offset order (``natural``; the native
+        solve's x).  IndexError for a pixel id out of range, ValueError for a label."""
+        torch = self.torch
+        G = int(n_labels)
+        if labels.numel() != self.n_offsets or labels.dtype != torch.int32:
+            raise ValueError(f'split labels must be int32 with {self.n_offsets} values (one per offset)')
+        if G < 1 or G * self.npix >= 2 ** 31:
+            raise ValueError(f'n_labels * npix must lie in [1, 2^31), not {G} * {self.npix}')
+        out = [self.empty(G * self.npix * self.nb) for _ in range(4)]        # written in full
+        N.bind_stream(self.ctx, self.dev)
+        rc = N.lib().comap_destripe_split_maps(self.ctx, N.dptr(self.pix), N.dptr(self.tod), N.dptr(self.w),
+                                               None if self.keep is None else N.dptr(self.keep), self._v(x),
+                                               N.dptr(labels), G, self.pix.numel(), self.L, self.npix, self.nb,
+                                               *(N.dptr(v) for v in out))
+        if rc == -3:
+            raise IndexError(f'pixel index out of range for a map of {self.npix} pixels '
+                             f'(valid: -{self.npix} .. {self.npix - 1})')
+        if rc == -4:
+            raise ValueError(f'split label out of range (valid: -1 .. {G - 1})')
+        N.check(rc, self.ctx, 'comap_destripe_split_maps')
+        return tuple(out)
+
+    def split_div(self, num, nnum, weight):
+        """(map, naive) = (num, naive_num) / weight where weight != 0, else the numerator."""
+        n = num.numel()
+        m, nv = self.empty(n), self.empty(n)
+        self._c('comap_destripe_split_div', self.ctx, N.dptr(num), N.dptr(nnum), N.dptr(weight), n, N.dptr(m),
+                N.dptr(nv))
+        return m, nv
+
     # ---- single-rank native solve (no Python per iteration)
     def solve_native(self, threshold, niter):
         """x [N/L * nb], iterations per band (list), maps {k: [npix * nb]} (interleaved)."""
@@ -592,6 +626,89 @@ def _ranks_agree(d, error, held=None):
                 raise error
             raise ValueError(f'ground template set-up failed on rank {rank}: {err[0]}: {err[1]}')
     merge_ground_tables([t for _, t in everyone])
+
+
+SPLIT_KEYS = ('map', 'naive', 'weight', 'hits')
+
+
+def _split_agree(d, error, values=None):
+    """The split maps' exchange across ranks: every rank's status (``error``: its exception or
+    None), so that all ranks raise or none does, and every rank's ``values`` (its label values,
+    or None), which are returned in rank order."""
+    everyone = [None] * d.get_world_size()
+    d.all_gather_object(everyone, (None if error is None else (type(error).__name__, str(error)), values))
+    for rank, (err, _) in enumerate(everyone):
+        if err is not None:
+            if rank == d.get_rank():
+                raise error
+            raise ValueError(f'split maps failed on rank {rank}: {err[0]}: {err[1]}')
+    return [v for _, v in everyone]
+
+
+def _offset_values(by, feedid, obsids, offset_length):
+    """The feed (by='feed') or observation (by='obsid') of every offset, [N/L]; ValueError when
+    it changes inside an offset or the samples are no whole offsets."""
+    if by not in ('feed', 'obsid'):
+        raise ValueError(f"split must be 'feed' or 'obsid', not {by!r}")
+    v = np.asarray(feedid if by == 'feed' else obsids).reshape(-1)
+    L = int(offset_length)
+    if L < 1 or v.size % L:
+        raise ValueError(f'{v.size} samples are not a multiple of offset_length {L}')
+    v = v.reshape(-1, L)
+    if v.size and np.any(v != v[:, :1]):
+        bad = int(np.nonzero(np.any(v != v[:, :1], axis=1))[0][0])
+        raise ValueError(f'offset {bad} straddles two {by}s: a split map needs every offset inside one')
+    return v[:, 0] if v.size else v.reshape(-1)
+
+
+def _labels_in(by, v, values):
+    """(labels int32, names) of the per-offset values ``v`` in the label set ``values``."""
+    members = np.unique(np.asarray(values).reshape(-1))
+    lab = np.searchsorted(members, v)
+    inside = lab < members.size
+    inside[inside] = members[lab[inside]] == v[inside]
+    lab = np.where(inside, lab, -1).astype(np.int32)
+    return lab, [f'Feed{int(m):02d}' if by == 'feed' else f'Obs{int(m)}' for m in members]
+
+
+def split_labels(by, feedid, obsids, offset_length, values=None):
+    """Split-map label of every offset: (labels int32 [N/L], names).
+
+    by='feed': label j for feed np.unique(feedid)[j], named f'Feed{feed:02d}' (the reference's
+    spelling, Destriper.py:487-501); by='obsid': label i for observation np.unique(obsids)[i],
+    named f'Obs{int(obsid)}'.  ``values`` fixes the label set instead (sorted and made unique;
+    ranks pass the union over ranks, so that label g means the same on every rank): a member
+    without samples is a label that owns no offset, and a sample whose feed / observation is not
+    a member gets label -1 (in no split).  The device pass works on whole offsets, so a feed or
+    observation that changes inside an offset raises ValueError, as do per-sample arrays whose
+    length is no multiple of offset_length (as ``ground_groups``)."""
+    v = _offset_values(by, feedid, obsids, offset_length)
+    return _labels_in(by, v, v if values is None else values)
+
+
+def split_specs(split, feedid, obsids, offset_length):
+    """run_destriper's ``split`` ('feed', 'obsid' or a list of these) as [(labels, names)] per
+    requested split, the label values being the union over ranks; a rank's ValueError (a label
+    changing inside an offset, ...) is raised on every rank.  None / empty: None."""
+    if split is None or (not isinstance(split, str) and len(split) == 0):
+        return None
+    kinds = [split] if isinstance(split, str) else list(split)
+    if feedid is None or obsids is None:
+        raise ValueError('split maps need feedid and obsids')
+    d = _dist()
+    ranks = d is not None and d.get_world_size() > 1
+    error, per_offset, values = None, None, None
+    try:
+        per_offset = [_offset_values(by, feedid, obsids, offset_length) for by in kinds]
+        values = [np.unique(v) for v in per_offset]
+    except ValueError as e:
+        if not ranks:
+            raise
+        error = e
+    if ranks:
+        every = _split_agree(d, error, values)
+        values = [np.concatenate([r[i] for r in every]) for i in range(len(kinds))]
+    return [_labels_in(by, v, vals) for by, v, vals in zip(kinds, per_offset, values)]
 
 
 class GroundOps(_Vectors):
@@ -836,10 +953,14 @@ class DeviceDestriper:
     With ``ground=`` across ranks the problem is always sharded, whatever COMAP_DS_RANKS says
     (``gather`` and ``auto`` are not supported with the ground template; a ``gather`` request
     falls back to shard with a warning): every rank must hold whole (observation, feed)
-    groups, whose offsets, slopes and levels are then rank-local unknowns."""
+    groups, whose offsets, slopes and levels are then rank-local unknowns.
+
+    With ``split=`` across ranks the problem is always sharded too (``gather`` warns and shards,
+    ``auto`` is ignored): each rank bins its own samples with its own offsets and the sums are
+    added across ranks."""
 
     def __init__(self, pixels, tod, weights, offset_length, npix, device=None, keep=None, map_shape=None,
-                 ground=None):
+                 ground=None, split=None):
         """map_shape (ny, nx): the map's row-major layout (CAR / WCS maps), when known; the
         operator then runs on a 2-D tiled internal pixel order (tiled_layout) and the maps
         come back in the caller's order.
@@ -849,9 +970,21 @@ class DeviceDestriper:
         The fit is per file and feed, hence local to the rank that holds the file: across ranks
         every (observation, feed) must lie on one rank (ValueError on every rank otherwise, as
         for any rank's set-up error), and rank 0's res['ground'] is the merged table of all
-        ranks (merge_ground_tables; None on the others)."""
+        ranks (merge_ground_tables; None on the others).
+        split (labels, n_labels): also bin per-label maps of tod - F x with the solve's own
+        offsets (the reference's "Create individual feed maps too" block, Destriper.py:487-501;
+        comap_destripe_split_maps): ``labels`` holds one int32 per offset in [-1, n_labels), -1
+        leaving the offset out of every split (``split_labels`` makes them by feed or by
+        observation; across ranks label g must mean the same on every rank).  solve() then adds
+        res['splits'] = {'map', 'naive', 'weight', 'hits'}, each [n_labels, npix] (one band) or
+        [n_bands, n_labels, npix], in the caller's pixel order.  A list of such pairs gives a
+        list of such dicts.  Not with ``ground``: the residual would need the fitted template
+        per sample."""
         self.layout, self.okey = None, None
         self.ground = None
+        self.split = None
+        if split is not None and ground is not None:
+            raise NotImplementedError('split maps with the ground template are not supported')
         T = int(os.environ.get('COMAP_DS_TILE', str(TILE)))
         if T > 0 and T & (T - 1):
             # the Morton code inside a tile interleaves log2(T) bits: for another T it would
@@ -873,13 +1006,27 @@ class DeviceDestriper:
         if ground is not None and ranks and os.environ.get('COMAP_DS_RANKS', 'shard') == 'gather':
             import warnings
             warnings.warn('COMAP_DS_RANKS=gather is not supported with the ground template: sharding')
+        if split is not None and ranks and os.environ.get('COMAP_DS_RANKS', 'shard') == 'gather':
+            import warnings
+            warnings.warn('COMAP_DS_RANKS=gather is not supported with split maps: sharding')
         if ranks:
-            if ground is None and self._choose_gather(d, pixels, tod, offset_length):
+            if ground is None and split is None and self._choose_gather(d, pixels, tod, offset_length):
                 self._gather(d, pixels, tod, weights, keep, offset_length, npix, device)
                 return
             if os.environ.get('COMAP_DS_COMPACT', '1') != '0':
                 pixels, npix = self._compact(pixels, int(npix), device)
         self.ops = N.retry_oom(DeviceOps, pixels, tod, weights, offset_length, npix, device, keep, self.okey)
+        if split is not None:
+            # (a rank's bad labels must fail every rank, as a ground set-up error does)
+            error = None
+            try:
+                self._set_split(split)
+            except ValueError as e:
+                if not ranks:
+                    raise
+                error = e
+            if ranks:
+                _split_agree(d, error)
         if ground is not None:
             az, feedid, obsids = ground
             # across ranks, a rank that raised here alone would leave its peers in a collective:
@@ -897,6 +1044,74 @@ class DeviceDestriper:
             if ranks:
                 _ranks_agree(d, error, table)
             self.ground = (uobs, ufeed)
+
+    def _set_split(self, split):
+        """self.split = [(int32 CUDA labels [N/L], n_labels)]; self.split_single: the caller
+        passed one pair, not a list.  Host labels are range-checked here, device labels by the
+        pass itself (ValueError either way)."""
+        torch = self.ops.torch
+        self.split_single = isinstance(split, tuple)
+        out = []
+        for labels, n_labels in ([split] if self.split_single else split):
+            G = int(n_labels)
+            if not isinstance(labels, torch.Tensor):
+                labels = np.asarray(labels).reshape(-1)
+                if labels.size and (int(labels.max()) >= G or int(labels.min()) < -1):
+                    raise ValueError(f'split label out of range (valid: -1 .. {G - 1})')
+            t = self.ops._t(labels, torch.int32)
+            if t.numel() != self.ops.n_offsets:
+                raise ValueError(f'split labels: one per offset ({self.ops.n_offsets}), not {t.numel()}')
+            if G < 1 or G * self.ops.npix >= 2 ** 31:
+                raise ValueError(f'n_labels * npix must lie in [1, 2^31), not {G} * {self.ops.npix}')
+            out.append((t, G))
+        self.split = out
+
+    def _split_maps(self, x, to_host=False):
+        """res['splits'] for the solved offsets ``x`` ([N/L * nb], the caller's order): per
+        requested split the rank's sums (DeviceOps.split_maps) added across ranks, divided, and
+        laid out as the maps are: expanded from the compacted pixels, in the caller's pixel
+        order, [n_labels, npix] or [n_bands, n_labels, npix].  to_host: host arrays on rank 0,
+        None on the others."""
+        ops = self.ops
+        d = _dist()
+        rank = d.get_rank() if d is not None else 0
+        ranks = d is not None and d.get_world_size() > 1
+        out = []
+        for labels, G in self.split:
+            # (the pass itself checks device labels and pixel ids: across ranks its error must reach
+            # every rank before the sums' all-reduce, where the other ranks would wait for this one)
+            error = None
+            try:
+                num, nnum, weight, hits = ops.split_maps(x, labels, G)
+            except (ValueError, IndexError, N.NativeError) as e:
+                if not ranks:
+                    raise
+                error = e
+            if ranks:
+                _split_agree(d, error)
+            for v in (num, nnum, weight, hits):
+                torch_allreduce(v)
+            m, naive = ops.split_div(num, nnum, weight)
+            maps = {k: self._split_layout(v, G) for k, v in zip(SPLIT_KEYS, (m, naive, weight, hits))}
+            if to_host:
+                maps = maps_to_host(maps) if rank == 0 else None
+            out.append(maps)
+        return out[0] if self.split_single else out
+
+    def _split_layout(self, v, G):
+        """[G * npix_internal * nb] (label, pixel, band fastest) -> [G, npix] (one band) or
+        [n_bands, G, npix] in the caller's pixel order: _expand and _untile, every label at once."""
+        ops = self.ops
+        t = v.reshape(G, -1, ops.nb)
+        if self.hit_index is not None:
+            full = ops.torch.zeros((G, self.npix_full, ops.nb), dtype=v.dtype, device=v.device)
+            full[:, self.hit_index] = t
+            t = full
+        if self.layout is not None:
+            t = t.index_select(1, self.layout)
+        if not self.multi:
+            return t[:, :, 0].contiguous()
+        return t.permute(2, 0, 1)[:ops.n_bands].contiguous()
 
     # ---- rank policy
     def _choose_gather(self, d, pixels, tod, offset_length):
@@ -1081,12 +1296,20 @@ class DeviceDestriper:
             x, it, maps = ops.solve_native_host(threshold, niter, unmap=self.layout)
             maps['map2'] = maps['weight']
             if not self.multi:
-                return {'x': x, 'iters': it[0], 'maps': {k: v[0] for k, v in maps.items()}}
-            return {'x': ops.split_bands(x), 'iters': it, 'maps': maps}
+                res = {'x': x, 'iters': it[0], 'maps': {k: v[0] for k, v in maps.items()}}
+            else:
+                res = {'x': ops.split_bands(x), 'iters': it, 'maps': maps}
+            if self.split is not None:           # after the overlapped solve, on the device x
+                res['splits'] = self._split_maps(x, to_host=True)
+            return res
         if to_host:
             res = self.solve(threshold, niter)
             rank = d.get_rank() if d is not None else 0
             res['maps'] = maps_to_host(res['maps']) if rank == 0 else None
+            if self.split is not None:
+                sp = [res['splits']] if self.split_single else res['splits']
+                sp = [maps_to_host(m) if rank == 0 else None for m in sp]
+                res['splits'] = sp[0] if self.split_single else sp
             return res
         if self.gathered is not None:
             x, it, maps, nb, nbands = self._solve_gathered(d, threshold, niter)
@@ -1116,12 +1339,13 @@ class DeviceDestriper:
         if self.layout is not None:
             nbl = nb if self.gathered is not None else ops.nb
             maps = {k: self._untile(v, nbl) for k, v in maps.items()}
+        extra = {} if self.split is None else {'splits': self._split_maps(x)}
         if not self.multi:
             maps['map2'] = maps['weight']
-            return {'x': x, 'iters': it[0], 'maps': maps}
+            return {'x': x, 'iters': it[0], 'maps': maps, **extra}
         maps = {k: split(v) for k, v in maps.items()}
         maps['map2'] = maps['weight']
-        return {'x': split(x), 'iters': it, 'maps': maps}
+        return {'x': split(x), 'iters': it, 'maps': maps, **extra}
 
     def _finish_maps(self, op, u, h, nnum):
         """The device maps {'map', 'naive', 'weight', 'hits'} of solution ``u`` of operator ``op``
@@ -1204,7 +1428,7 @@ def maps_to_host(maps):
 
 def run_destriper(_pointing, _tod, _weights, offset_length, pixel_edges, az=None, el=None, ra=None, dec=None,
                   feedid=None, obsids=None, obsid_cuts=None, threshold=1e-6, niter=100, chi2_cutoff=100,
-                  special_weight=None, healpix=False, device=None, map_shape=None, ground=False):
+                  special_weight=None, healpix=False, device=None, map_shape=None, ground=False, split=None):
     """Destriper.run_destriper (Destriper.py:456-503) on the GPU.
 
     ``pixel_edges[-1] + 1`` is the map size (bin_offset_map, :169).  Returns
@@ -1216,7 +1440,13 @@ def run_destriper(_pointing, _tod, _weights, offset_length, pixel_edges, az=None
     op_Ax_with_ground, :265-336, which its run() leaves switched off); the result gains
     'Ground': {'obsids', 'feeds', 'slope', 'level', 'wrapped'}: across ranks (every
     (observation, feed) on one rank) rank 0 gets the merged table of all ranks' observations
-    and the other ranks None maps and 'Ground': None."""
+    and the other ranks None maps and 'Ground': None.
+    split='feed', 'obsid' or a list of these, an extension: the reference's commented "Create
+    individual feed maps too" block (:487-501), completed -- one {'map', 'naive', 'weight',
+    'hits'} entry per feed ('Feed01', ...) or observation ('Obs<obsid>') beside 'All', binned
+    from that subset's samples of tod - F x with the solve's own offsets (None maps on ranks
+    other than 0; across ranks the names are those of all ranks' feeds / observations), and
+    'offsets', the rank's solved offsets (host, [N/L])."""
     if special_weight is not None:
         raise NotImplementedError('special_weight is unused by run_destriper in the reference (:482)')
     import torch
@@ -1225,18 +1455,39 @@ def run_destriper(_pointing, _tod, _weights, offset_length, pixel_edges, az=None
     npix = int(pixel_edges[-1]) + 1
     if ground and (az is None or feedid is None or obsids is None):
         raise ValueError('ground=True needs az, feedid and obsids')
+    if ground and split:
+        raise NotImplementedError('split maps with the ground template are not supported')
+    specs = split_specs(split, feedid, obsids, offset_length)
     dd = DeviceDestriper(np.asarray(_pointing), np.asarray(_tod, dtype=np.float64),
                          np.asarray(_weights, dtype=np.float64), int(offset_length), npix, device, map_shape=map_shape,
-                         ground=(np.asarray(az, dtype=np.float64), feedid, obsids) if ground else None)
+                         ground=(np.asarray(az, dtype=np.float64), feedid, obsids) if ground else None,
+                         split=None if specs is None else [(lab, len(names)) for lab, names in specs])
     res = dd.solve(threshold, niter, to_host=True)
     maps = res['maps']
     if maps is None:                     # a rank other than 0
         maps = {'map': None, 'naive': None, 'weight': None, 'map2': None}
-    return {'All': maps, 'Ground': res['ground']} if ground else {'All': maps}
+    out = {'All': maps, 'Ground': res['ground']} if ground else {'All': maps}
+    if specs is not None:
+        out.update(_split_entries(specs, res['splits']))
+        out['offsets'] = res['x'].cpu().numpy()      # this rank's offsets, which its split maps were binned with
+    return out
+
+
+def _split_entries(specs, splits, band=None):
+    """{name: {'map', 'naive', 'weight', 'hits'}} of every label of every requested split
+    (``band``: of that band of a batched solve); None maps where the rank got none."""
+    out = {}
+    for (_, names), sp in zip(specs, splits):
+        for g, name in enumerate(names):
+            if sp is None:
+                out[name] = dict.fromkeys(SPLIT_KEYS)
+            else:
+                out[name] = {k: (sp[k][g] if band is None else sp[k][band][g]) for k in SPLIT_KEYS}
+    return out
 
 
 def run_destriper_bands(_pointing, _tods, _weights, offset_length, pixel_edges, keep=None, threshold=1e-6,
-                        niter=100, device=None, map_shape=None):
+                        niter=100, device=None, map_shape=None, split=None, feedid=None, obsids=None):
     """run_destriper for several sidebands on the same pointing in ONE batched
     device solve (the reference calls run_destriper once per band,
     run_destriper.py:146-189).  _tods/_weights [n_bands, N]; keep [n_bands, N/L]
@@ -1244,7 +1495,11 @@ def run_destriper_bands(_pointing, _tods, _weights, offset_length, pixel_edges, 
     {'All': maps} per band (host maps on rank 0, None maps on other ranks);
     band b's maps and iteration count are those of run_destriper on band b's
     own samples, and its offsets (``x``, rank 0: also under 'offsets') cover
-    the union of the bands' offsets (0 where band b dropped the offset)."""
+    the union of the bands' offsets (0 where band b dropped the offset).
+    split ('feed', 'obsid' or a list of these, with per-sample ``feedid`` and ``obsids``): each
+    band's dict also gets run_destriper's split-map entries, all bands' from one device pass
+    per split; a band's 'hits' leave out the offsets it dropped.  With split, ranks other than 0
+    get 'offsets' too (their own), as from run_destriper."""
     import torch
     if device is None:
         device = torch.cuda.current_device()
@@ -1252,19 +1507,24 @@ def run_destriper_bands(_pointing, _tods, _weights, offset_length, pixel_edges, 
     tods = np.asarray(_tods, dtype=np.float64)
     if tods.ndim != 2:
         raise ValueError('_tods must be [n_bands, N]')
+    specs = split_specs(split, feedid, obsids, offset_length)
     dd = DeviceDestriper(np.asarray(_pointing), tods, np.asarray(_weights, dtype=np.float64), int(offset_length), npix,
-                         device, keep=None if keep is None else np.asarray(keep, dtype=np.uint8), map_shape=map_shape)
+                         device, keep=None if keep is None else np.asarray(keep, dtype=np.uint8), map_shape=map_shape,
+                         split=None if specs is None else [(lab, len(names)) for lab, names in specs])
     res = dd.solve(threshold, niter, to_host=True)
     d = _dist()
     rank = d.get_rank() if d is not None else 0
     out = []
     hm = res['maps']
     for b in range(tods.shape[0]):
+        extra = {} if specs is None else _split_entries(specs, res['splits'], band=b)
         if rank != 0:
-            out.append({'All': {'map': None, 'naive': None, 'weight': None, 'map2': None}})
+            if specs is not None:        # every rank keeps the offsets its split sums were binned with
+                extra['offsets'] = res['x'][b].cpu().numpy()
+            out.append({'All': {'map': None, 'naive': None, 'weight': None, 'map2': None}, **extra})
             continue
         maps = {k: v[b] for k, v in hm.items()}
-        out.append({'All': maps, 'iters': res['iters'][b], 'offsets': res['x'][b].cpu().numpy()})
+        out.append({'All': maps, 'iters': res['iters'][b], 'offsets': res['x'][b].cpu().numpy(), **extra})
     return out
 
 

@@ -125,7 +125,8 @@ def main(filelistname, offset_length=50, feed_weights=None, prefix='fg9', output
          feeds=[1, 2, 3, 5, 6, 9, 11, 12, 13, 14, 15, 16, 17, 18, 19], nxpix=480, nypix=480,
          crval=['05:32:00.3', '+12:30:28.0'], crpix=[240, 240], ctype=['RA---CAR', 'DEC--CAR'],
          cdelt=[-0.016666, 0.016666], use_gain_filter=True, calibration=True, calibrator='TauA', threshold=1e-6,
-         niter=100, healpix=False, bands=(0, 1, 2, 3), store=None, device=None, batch_bands=True, ground=False):
+         niter=100, healpix=False, bands=(0, 1, 2, 3), store=None, device=None, batch_bands=True, ground=False,
+         split=None):
     """run_destriper.main (run_destriper.py:79-189).  ``store`` (tests) maps
     filename -> (datasets, attrs) instead of reading files; ``device`` is the
     rank's GPU (default: torch's current device, LOCAL_RANK under torchrun).
@@ -140,7 +141,17 @@ def main(filelistname, offset_length=50, feed_weights=None, prefix='fg9', output
     -- across ranks the merged table of all ranks' observations -- to
     <output_dir>/<prefix>_ground_band<iband>.npz and the band's entry gains 'Ground' (None on
     the other ranks).  Files are whole observations, so each (observation, feed) lies on the
-    one rank that holds the file."""
+    one rank that holds the file.
+    ``split`` ([Inputs] split_maps in the .ini: feed, obsid or both; absent = none): also map
+    every feed ('Feed01', ...) and / or observation ('Obs<obsid>') on its own, from its samples of
+    tod - F x with the solve's offsets (the reference's commented "Create individual feed maps
+    too" block, Destriper.py:487-501): each band's dict gains one entry per name and rank 0
+    writes <name>_<prefix>_Band<iband>.fits beside All_...; the band's dict also keeps 'offsets',
+    the rank's solved offsets the split maps were binned with.  Not together with ``ground``."""
+    if split is not None and isinstance(split, str):
+        split = [split]
+    if split and ground:
+        raise NotImplementedError('split_maps with ground_template is not supported')
     rank, size = _rank_size()
     if device is None:
         import torch
@@ -171,15 +182,17 @@ def main(filelistname, offset_length=50, feed_weights=None, prefix='fg9', output
         pixel_edges = _healpix_edges(r['pointing']) if healpix else np.arange(nxpix * nypix)
         res = run_destriper_bands(r['pointing'], r['tod'], r['weights'], offset_length, pixel_edges, keep=r['keep'],
                                   threshold=threshold, niter=niter, device=device,
-                                  map_shape=None if healpix else (nypix, nxpix))
+                                  map_shape=None if healpix else (nypix, nxpix), split=split or None,
+                                  feedid=r['feedid'], obsids=r['obsids'])
         for iband, maps in zip(bands, res):
-            maps = {'All': maps['All']}
+            sky = {k: v for k, v in maps.items() if k not in ('iters', 'offsets')}    # 'All' and the split maps
             if rank == 0:
                 if healpix:
-                    write_map_healpix(prefix, maps, r['remapping_array'], map_info, output_dir, iband)
+                    write_map_healpix(prefix, sky, r['remapping_array'], map_info, output_dir, iband)
                 else:
-                    write_map(prefix, maps, map_info, output_dir, iband)
-            out[iband] = maps
+                    write_map(prefix, sky, map_info, output_dir, iband)
+            # (with split maps the band's entry keeps the offsets they were binned with)
+            out[iband] = dict(sky, offsets=maps['offsets']) if split else sky       # (on every rank, as per band)
         return out
     for iband in bands:
         tod, weights, pointing, remap, az, el, ra, dec, feedid, obsids = COMAPData.read_comap_data(
@@ -189,8 +202,9 @@ def main(filelistname, offset_length=50, feed_weights=None, prefix='fg9', output
         pixel_edges = _healpix_edges(pointing) if healpix else np.arange(nxpix * nypix)
         maps = run_destriper(pointing, tod, weights, offset_length, pixel_edges, az, el, ra, dec, feedid, obsids,
                              obsid_cuts, threshold=threshold, niter=niter, chi2_cutoff=20,
-                             device=device, map_shape=None if healpix else (nypix, nxpix), ground=ground)
-        sky = {'All': maps['All']}               # (the writers iterate the dict: the maps only)
+                             device=device, map_shape=None if healpix else (nypix, nxpix), ground=ground,
+                             split=split or None)
+        sky = {k: v for k, v in maps.items() if k not in ('Ground', 'offsets')}    # (the writers iterate the dict: the maps only)
         if rank == 0:
             if healpix:
                 write_map_healpix(prefix, sky, remap, map_info, output_dir, iband)
@@ -211,6 +225,7 @@ def cli(argv):
     feeds = params['feeds']
     feeds = [int(f) for f in (feeds if isinstance(feeds, list) else [feeds])]
     as_list = lambda v: v if isinstance(v, list) else [v]  # noqa: E731
+    split = params.get('split_maps')             # 'feed', 'obsid' or both (a list); absent or None: no split maps
     return main(params['filelistname'], offset_length=int(params['offset_length']), prefix=params['prefix'],
                 output_dir=params['output_dir'], feeds=feeds, feed_weights=params['feed_weights'],
                 nxpix=int(params['nxpix']), nypix=int(params['nypix']), crval=as_list(params['crval']),
@@ -218,4 +233,5 @@ def cli(argv):
                 use_gain_filter=p['ReadData']['use_gain_filter'], calibration=p['ReadData']['calibration'],
                 calibrator=p['ReadData']['calibrator'], threshold=10 ** float(params['threshold']),
                 niter=int(params['niter']), healpix=params['healpix'],
-                ground=bool(params.get('ground_template', False)))
+                ground=bool(params.get('ground_template', False)),
+                split=[str(k) for k in as_list(split)] if split else None)

@@ -455,6 +455,31 @@ int comap_destripe_ground_dist_update(comap_ground *g, double *scal_dev, double 
 int comap_destripe_ground_dist_direction(comap_ground *g, double *scal_dev, double *p_dev, const double *r_dev,
                                          int32_t *flags_dev);
 
+/* ------------------------------------------------------------ split maps (Destriper.py:487-501) */
+/* Per-label maps of a solved problem, all labels in one pass: the reference's (commented)
+ * "Create individual feed maps too" block for any labelling of the offsets.  label_dev[o] in
+ * [-1, n_labels) is offset o's label (-1: in no split).  For label g, band b, pixel p, over the
+ * samples t with label[t / L] == g and pixels[t] == p in increasing t, each operation rounded to
+ * f64 on its own (binValues' order, bit for bit):
+ *   weight += w[b][t];  naive_num += tod[b][t] w[b][t];  num += (tod[b][t] - x[t / L][b]) w[b][t];
+ *   hits += 1 (only where keep_dev == NULL or keep[b][t / L] != 0).
+ * Negative pixel ids are never binned.  tod / weights [n_bands][N], keep [n_bands][N / L] or NULL,
+ * x [N / L][n_bands] in the caller's offset order (comap_destripe_solve's, or
+ * comap_destripe_offsets_natural's); the four outputs [n_labels][npix][n_bands], band fastest, are
+ * written in full (0 where a label has no sample in a pixel).  n_bands in {1, 2, 4};
+ * n_labels npix < 2^31; N < 2^31.  Deterministic (stable sort, no floating-point atomics).
+ * Returns -3 for a pixel id outside [-npix, npix), -4 for a label outside [-1, n_labels).
+ * Synchronises once (segment count and error flags). */
+int comap_destripe_split_maps(comap_ctx *ctx, const int32_t *pixels_dev, const double *tod_dev,
+                              const double *weights_dev, const uint8_t *keep_dev, const double *x_dev,
+                              const int32_t *label_dev, int32_t n_labels, int64_t n_samples, int32_t offset_length,
+                              int64_t npix, int32_t n_bands, double *num_dev, double *naive_num_dev,
+                              double *weight_dev, double *hits_dev);
+/* map = num / weight where weight != 0, else num; naive likewise from naive_num
+ * (comap_destripe_div_map's rule) over n values: after the sums have been added across ranks. */
+int comap_destripe_split_div(comap_ctx *ctx, const double *num_dev, const double *naive_num_dev,
+                             const double *weight_dev, int64_t n, double *map_dev, double *naive_dev);
+
 /* ------------------------------------------------------------ destriper data prep (COMAPData.py) */
 /* One Level-2 file's inputs to comap_prep_gather (device pointers).  Output row r
  * (0 <= r < n_rows = len(output_feed_index)) takes its tod / weights / az / el /
