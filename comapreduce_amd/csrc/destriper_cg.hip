@@ -891,9 +891,14 @@ extern "C" int comap_destripe_dist_bin(comap_destriper *d, const double *p, doub
 // The rest of the iteration is the native solve's kernels, with the p.q and r.r block
 // partials (one slot per block, kDistParts per band, zero beyond the grid) all-reduced
 // between them.  Adding the zero slots changes no bit, so on one rank the iterates equal
-// comap_destripe_solve's.
-constexpr int kDistParts = 1024;   // >= kProjBlocks, kUpdBlocks
-static_assert(kDistParts >= kProjBlocks && kDistParts >= kUpdBlocks, "partial slots");
+// comap_destripe_solve's -- as long as the projection runs the native solve's grid, i.e. the
+// slots hold it: 2 kProjBlocks, the sliced-ELLPACK projection's default grid cap below 2 M
+// offsets (1024 slots capped its grid from 262 144 offsets on, and the p.q partials, hence
+// every iterate, then differed from the native solve's in the last bits).  A problem whose
+// projection grid is larger still (2 M offsets and more, COMAP_DS_PB above 2048) runs it on
+// kDistParts blocks here.
+constexpr int kDistParts = 2 * kProjBlocks;   // >= the default projection grids, kUpdBlocks
+static_assert(kDistParts >= 2 * kProjBlocks && kDistParts >= kUpdBlocks && kDistParts <= kPartMax, "partial slots");
 
 extern "C" int32_t comap_destripe_dist_parts(void) { return kDistParts; }
 
