@@ -120,6 +120,9 @@ _SIGS = {
     'comap_destripe_split_maps': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
                                           c_int64, c_int32, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     'comap_destripe_split_div': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    'comap_destripe_residuals': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_int32, c_int64, c_int32, c_int64, c_int32, c_void_p, c_void_p, c_void_p,
+                                         c_void_p]),
     'comap_prep_auto_rms': (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int64, c_void_p]),
     'comap_prep_percentiles': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_int64,
                                        c_void_p]),

@@ -57,6 +57,22 @@ def _to_tensor(a, dev, dt):
     return t.to(device=dev, dtype=dt)
 
 
+def lane_tree_sum(v):
+    """The sum of ``v`` in the residual pass's lane-tree order (comap_destripe_residuals), in
+    NumPy: lane l of 64 adds v[l], v[l + 64], v[l + 128], ... in that order from +0.0; then for
+    s = 32, 16, 8, 4, 2, 1: a[l] = a[l] + a[l ^ s]; the result is lane 0's.  I.e. ``v`` padded
+    with +0.0 to a multiple of 64 as [K, 64], its rows added in order, then folded."""
+    v = np.asarray(v, dtype=np.float64).reshape(-1)
+    rows = np.zeros((-(-v.size // 64), 64))
+    rows.reshape(-1)[:v.size] = v
+    a = np.zeros(64)
+    for row in rows:
+        a = a + row
+    for s in (32, 16, 8, 4, 2, 1):
+        a = a[:s] + a[s:2 * s]
+    return float(a[0])
+
+
 class TimedAllreduce:
     """torch_allreduce with every call bracketed by HIP events on the current stream (the
     stream the CG kernels run on, which waits for the collective): the measured
@@ -504,6 +520,47 @@ class DeviceOps(_Vectors):
                 N.dptr(nv))
         return m, nv
 
+    # ---- residual chi-squared (comap_destripe_residuals)
+    def residuals(self, x, m, group=None, n_groups=0):
+        """(off_sum, off_cnt, grp_sum, grp_cnt) of this rank's samples against the solved offsets
+        ``x`` ([N/L * nb], the CALLER's offset order: ``natural``, the native solve's x) and the
+        map ``m`` ([npix * nb] in the problem's internal pixel layout, i.e. before the
+        destriper's expansion and un-tiling): per offset and band the sum of (w r) r, r = (tod -
+        x) - m[pix], over the counted samples (pix >= 0, w > 0, the band kept the offset) in the
+        lane-tree order (``lane_tree_sum``) and their number, [N/L * nb] float64 / int32; per
+        group the lane-tree sum of its offsets' sums in increasing offset and the sum of their
+        counts, [n_groups * nb] float64 / int64 (None without ``group``: int32 CUDA [N/L] in
+        [-1, n_groups), -1 = in no group).  A non-finite tod makes its sums NaN.  IndexError for a
+        pixel id out of range, ValueError for a label."""
+        torch = self.torch
+        G = int(n_groups)
+        if group is not None:
+            if group.numel() != self.n_offsets or group.dtype != torch.int32:
+                raise ValueError(f'residual groups must be int32 with {self.n_offsets} values (one per offset)')
+            if G < 1:
+                raise ValueError(f'n_groups must be >= 1 with group labels, not {G}')
+        elif G != 0:
+            raise ValueError('n_groups without group labels')
+        n = self.n_offsets * self.nb
+        off_sum, off_cnt = self.empty(n), N.device_empty(n, torch.int32, self.dev)     # written in full
+        grp_sum = grp_cnt = None
+        if group is not None:
+            grp_sum, grp_cnt = self.empty(G * self.nb), N.device_empty(G * self.nb, torch.int64, self.dev)
+        N.bind_stream(self.ctx, self.dev)
+        rc = N.lib().comap_destripe_residuals(self.ctx, N.dptr(self.pix), N.dptr(self.tod), N.dptr(self.w),
+                                              None if self.keep is None else N.dptr(self.keep), self._v(x),
+                                              self._m(m), None if group is None else N.dptr(group), G,
+                                              self.pix.numel(), self.L, self.npix, self.nb, N.dptr(off_sum),
+                                              N.dptr(off_cnt), None if group is None else N.dptr(grp_sum),
+                                              None if group is None else N.dptr(grp_cnt))
+        if rc == -3:
+            raise IndexError(f'pixel index out of range for a map of {self.npix} pixels '
+                             f'(valid: -{self.npix} .. {self.npix - 1})')
+        if rc == -4:
+            raise ValueError(f'residual group label out of range (valid: -1 .. {G - 1})')
+        N.check(rc, self.ctx, 'comap_destripe_residuals')
+        return off_sum, off_cnt, grp_sum, grp_cnt
+
     # ---- single-rank native solve (no Python per iteration)
     def solve_native(self, threshold, niter):
         """x [N/L * nb], iterations per band (list), maps {k: [npix * nb]} (interleaved)."""
@@ -631,7 +688,7 @@ def _ranks_agree(d, error, held=None):
 SPLIT_KEYS = ('map', 'naive', 'weight', 'hits')
 
 
-def _split_agree(d, error, values=None):
+def _split_agree(d, error, values=None, what='split maps'):
     """The split maps' exchange across ranks: every rank's status (``error``: its exception or
     None), so that all ranks raise or none does, and every rank's ``values`` (its label values,
     or None), which are returned in rank order."""
@@ -641,8 +698,33 @@ def _split_agree(d, error, values=None):
         if err is not None:
             if rank == d.get_rank():
                 raise error
-            raise ValueError(f'split maps failed on rank {rank}: {err[0]}: {err[1]}')
+            raise ValueError(f'{what} failed on rank {rank}: {err[0]}: {err[1]}')
     return [v for _, v in everyone]
+
+
+def residual_group_labels(feedid, obsids, offset_length):
+    """The residual table's (observation, feed) group of every offset: (gid int32 [N/L],
+    unique_obsids, unique_feeds), ``ground_groups``' labels (group = i n_feeds + j; an offset
+    that straddles two groups raises ValueError) -- across ranks over the union of all ranks'
+    observations and feeds, taken as ``split_specs`` takes its labels, so that group g means the
+    same on every rank; a rank's ValueError is raised on every rank."""
+    d = _dist()
+    ranks = d is not None and d.get_world_size() > 1
+    error, mine = None, None
+    try:
+        mine = ground_groups(feedid, obsids, offset_length)
+    except ValueError as e:
+        if not ranks:
+            raise
+        error = e
+    if not ranks:
+        return mine
+    every = _split_agree(d, error, None if mine is None else (mine[1], mine[2]), what='residuals')
+    gid, uobs, ufeed = mine
+    aobs = np.unique(np.concatenate([np.asarray(v[0]).reshape(-1) for v in every]))
+    afeed = np.unique(np.concatenate([np.asarray(v[1]).reshape(-1) for v in every]))
+    i, j = np.searchsorted(aobs, uobs)[gid // ufeed.size], np.searchsorted(afeed, ufeed)[gid % ufeed.size]
+    return (i * afeed.size + j).astype(np.int32), aobs, afeed
 
 
 def _offset_values(by, feedid, obsids, offset_length):
@@ -957,10 +1039,12 @@ class DeviceDestriper:
 
     With ``split=`` across ranks the problem is always sharded too (``gather`` warns and shards,
     ``auto`` is ignored): each rank bins its own samples with its own offsets and the sums are
-    added across ranks."""
+    added across ranks.  The same holds with ``residuals=`` / ``residual_cut=``: each rank's
+    residual pass runs on its own samples and offsets against the global map, the group sums and
+    counts are added across ranks, and every rank takes the same cut."""
 
     def __init__(self, pixels, tod, weights, offset_length, npix, device=None, keep=None, map_shape=None,
-                 ground=None, split=None):
+                 ground=None, split=None, residuals=None, residual_groups=None, residual_cut=None):
         """map_shape (ny, nx): the map's row-major layout (CAR / WCS maps), when known; the
         operator then runs on a 2-D tiled internal pixel order (tiled_layout) and the maps
         come back in the caller's order.
@@ -979,12 +1063,35 @@ class DeviceDestriper:
         res['splits'] = {'map', 'naive', 'weight', 'hits'}, each [n_labels, npix] (one band) or
         [n_bands, n_labels, npix], in the caller's pixel order.  A list of such pairs gives a
         list of such dicts.  Not with ``ground``: the residual would need the fitted template
-        per sample."""
+        per sample.
+        residuals: True -- one group per (observation, feed), from residual_groups=(feedid,
+        obsids) per sample (``residual_group_labels``) -- or (gid, n_groups), one int32 label per
+        offset in [-1, n_groups), -1 = in no group: after the solve, the residual chi-squared of
+        tod - F x - P m per group (comap_destripe_residuals; across ranks each rank's own samples
+        and offsets against the global map, the group sums added over ranks).  solve() then adds
+        res['residuals'] = {'chi2', 'sum', 'count'} ([n_groups] or [n_bands, n_groups]; chi2 =
+        sum / count where count > 0, else 0) and {'offset_sum', 'offset_count'} ([N/L] or
+        [n_bands, N/L], this rank's offsets).  A non-finite tod makes its group's chi2 NaN.
+        residual_cut c (a float; implies residuals): group g of band b is cut when count > 0 and
+        not chi2 <= c (so a NaN is cut); if any is, the operator is rebuilt with the cut groups'
+        weights zeroed and their offsets dropped (keep 0: they leave the hit map), solved ONCE
+        more (not iterated) and the residuals recomputed; res['residuals'] gains 'cut' (bool) and
+        'chi2_first' (the first pass's chi2).  Not with ``ground`` either."""
         self.layout, self.okey = None, None
         self.ground = None
         self.split = None
+        self.resid, self.resid_cut, self.resid_axes = None, None, None
         if split is not None and ground is not None:
             raise NotImplementedError('split maps with the ground template are not supported')
+        if residual_cut is not None and residuals is None:
+            residuals = True
+        if residuals is False:
+            residuals = None
+        if residuals is not None and ground is not None:
+            raise NotImplementedError('residuals with the ground template are not supported: the residual '
+                                      'would need the fitted template per sample')
+        if residuals is True and residual_groups is None:
+            raise ValueError('residuals=True needs residual_groups=(feedid, obsids)')
         T = int(os.environ.get('COMAP_DS_TILE', str(TILE)))
         if T > 0 and T & (T - 1):
             # the Morton code inside a tile interleaves log2(T) bits: for another T it would
@@ -1009,13 +1116,33 @@ class DeviceDestriper:
         if split is not None and ranks and os.environ.get('COMAP_DS_RANKS', 'shard') == 'gather':
             import warnings
             warnings.warn('COMAP_DS_RANKS=gather is not supported with split maps: sharding')
+        if residuals is not None and ranks and os.environ.get('COMAP_DS_RANKS', 'shard') == 'gather':
+            import warnings
+            warnings.warn('COMAP_DS_RANKS=gather is not supported with residuals: sharding')
         if ranks:
-            if ground is None and split is None and self._choose_gather(d, pixels, tod, offset_length):
+            if ground is None and split is None and residuals is None \
+                    and self._choose_gather(d, pixels, tod, offset_length):
                 self._gather(d, pixels, tod, weights, keep, offset_length, npix, device)
                 return
             if os.environ.get('COMAP_DS_COMPACT', '1') != '0':
                 pixels, npix = self._compact(pixels, int(npix), device)
         self.ops = N.retry_oom(DeviceOps, pixels, tod, weights, offset_length, npix, device, keep, self.okey)
+        if residuals is not None:
+            self.resid_cut = None if residual_cut is None else float(residual_cut)
+            if residuals is True:
+                gid, uobs, ufeed = residual_group_labels(*residual_groups, offset_length)   # (fails on every rank)
+                self.resid_axes = (uobs, ufeed)
+                residuals = (gid, uobs.size * ufeed.size)
+            # (a rank's bad labels must fail every rank, as for the split labels)
+            error = None
+            try:
+                self.resid = self._labels(*residuals, 'residual group')
+            except ValueError as e:
+                if not ranks:
+                    raise
+                error = e
+            if ranks:
+                _split_agree(d, error, what='residuals')
         if split is not None:
             # (a rank's bad labels must fail every rank, as a ground set-up error does)
             error = None
@@ -1112,6 +1239,91 @@ class DeviceDestriper:
         if not self.multi:
             return t[:, :, 0].contiguous()
         return t.permute(2, 0, 1)[:ops.n_bands].contiguous()
+
+    # ---- residual chi-squared
+    def _labels(self, labels, n_labels, what):
+        """(int32 CUDA labels [N/L], n_labels); host labels are range-checked here, device labels
+        by the pass itself (ValueError either way)."""
+        torch = self.ops.torch
+        G = int(n_labels)
+        if not isinstance(labels, torch.Tensor):
+            labels = np.asarray(labels).reshape(-1)
+            if labels.size and (int(labels.max()) >= G or int(labels.min()) < -1):
+                raise ValueError(f'{what} label out of range (valid: -1 .. {G - 1})')
+        t = self.ops._t(labels, torch.int32)
+        if t.numel() != self.ops.n_offsets:
+            raise ValueError(f'{what} labels: one per offset ({self.ops.n_offsets}), not {t.numel()}')
+        if G < 1:
+            raise ValueError(f'{what}: n_groups must be >= 1, not {G}')
+        return t, G
+
+    def _residuals(self, x, m):
+        """res['residuals'] (device tensors) for the solved offsets ``x`` ([N/L * nb], the caller's
+        order) and the global map ``m`` ([npix_internal * nb], before _expand / _untile): the rank's
+        pass (DeviceOps.residuals), the group sums and counts added across ranks -- with whole
+        files per rank a group has one contributing rank, so the sum is exact."""
+        ops = self.ops
+        torch = ops.torch
+        d = _dist()
+        ranks = d is not None and d.get_world_size() > 1
+        gid, G = self.resid
+        # (the pass itself checks device labels and pixel ids: across ranks its error must reach
+        # every rank before the all-reduce, where the other ranks would wait for this one)
+        error = None
+        try:
+            off_sum, off_cnt, grp_sum, grp_cnt = ops.residuals(x, m, gid, G)
+        except (ValueError, IndexError, N.NativeError) as e:
+            if not ranks:
+                raise
+            error = e
+        if ranks:
+            _split_agree(d, error, what='residuals')
+            torch_allreduce(grp_sum)
+            torch_allreduce(grp_cnt)
+        lay = (lambda v: v.reshape(-1, ops.nb).t()[:ops.n_bands].contiguous()) if self.multi \
+            else (lambda v: v.reshape(-1, ops.nb)[:, 0].contiguous())
+        s, c = lay(grp_sum), lay(grp_cnt)
+        chi2 = torch.where(c > 0, s / torch.where(c > 0, c, torch.ones_like(c)).to(torch.float64), torch.zeros_like(s))
+        return {'chi2': chi2, 'sum': s, 'count': c, 'offset_sum': lay(off_sum), 'offset_count': lay(off_cnt)}
+
+    def _cut_groups(self, cut):
+        """The operator rebuilt without the cut groups (``cut`` bool [n_bands, G] or [G]): band
+        b's weights zeroed on every sample of its cut groups and keep[b][o] = 0 on their offsets."""
+        ops = self.ops
+        torch = ops.torch
+        gid, G = self.resid
+        nbo, NO, L = ops.n_bands, ops.n_offsets, ops.L
+        cut2 = cut.reshape(nbo, G)
+        idx = gid.to(torch.int64).clamp(min=0)
+        gone = cut2[:, idx] & (gid >= 0)[None, :]                           # [n_bands, N/L]
+        w = ops.w[:nbo].clone()
+        w.view(nbo, NO, L)[gone] = 0.0
+        keep = torch.ones((nbo, NO), dtype=torch.uint8, device=ops.dev) if ops.keep is None else ops.keep[:nbo].clone()
+        keep[gone] = 0
+        pix, tod, npix, dev = ops.pix, ops.tod[:nbo], ops.npix, ops.dev.index
+        self.ops = None                                                     # (the old problem's buffers go first)
+        del ops
+        self.ops = N.retry_oom(DeviceOps, pix, tod, w, L, npix, dev, keep, self.okey)
+
+    def solve(self, threshold=1e-6, niter=100, to_host=False, allreduce=None):
+        """to_host: maps as host NumPy arrays (rank 0; None on the others) -- one
+        rank solving alone overlaps their copy with the CG (solve_native_host).
+        allreduce: the sharded CG's sum across ranks (default torch_allreduce; bench.py
+        passes a TimedAllreduce to measure the per-iteration collective cost).
+        With ``residual_cut`` the solve runs a second time when the first pass cut a group."""
+        res = self._solve(threshold, niter, to_host, allreduce)
+        if self.resid is None or self.resid_cut is None:
+            return res
+        torch = self.ops.torch
+        r = res['residuals']
+        chi2, count = (torch.as_tensor(r[k]) for k in ('chi2', 'count'))
+        cut = (count > 0) & ~(chi2 <= self.resid_cut)                       # (a NaN chi2 is cut)
+        if bool(cut.any()):
+            self._cut_groups(cut.to(self.ops.dev))
+            res = self._solve(threshold, niter, to_host, allreduce)
+        conv = (lambda v: v.cpu().numpy()) if to_host else (lambda v: v)
+        res['residuals'].update(cut=conv(cut), chi2_first=conv(chi2))
+        return res
 
     # ---- rank policy
     def _choose_gather(self, d, pixels, tod, offset_length):
@@ -1283,16 +1495,15 @@ class DeviceDestriper:
     def sell_entries(self):
         return self.ops.sell_entries()
 
-    def solve(self, threshold=1e-6, niter=100, to_host=False, allreduce=None):
-        """to_host: maps as host NumPy arrays (rank 0; None on the others) -- one
-        rank solving alone overlaps their copy with the CG (solve_native_host).
-        allreduce: the sharded CG's sum across ranks (default torch_allreduce; bench.py
-        passes a TimedAllreduce to measure the per-iteration collective cost)."""
+    def _solve(self, threshold, niter, to_host, allreduce):
+        """One solve() of the problem as it stands (see solve).  With residuals the single-rank
+        to_host call takes the general path: the overlapped solve_native_host never leaves the
+        device map in reach."""
         if self.ground is not None:
             return self._solve_ground(threshold, niter, to_host)
         d = _dist()
         ops = self.ops
-        if to_host and self.gathered is None and (d is None or d.get_world_size() == 1):
+        if to_host and self.gathered is None and (d is None or d.get_world_size() == 1) and self.resid is None:
             x, it, maps = ops.solve_native_host(threshold, niter, unmap=self.layout)
             maps['map2'] = maps['weight']
             if not self.multi:
@@ -1303,9 +1514,11 @@ class DeviceDestriper:
                 res['splits'] = self._split_maps(x, to_host=True)
             return res
         if to_host:
-            res = self.solve(threshold, niter)
+            res = self._solve(threshold, niter, False, None)
             rank = d.get_rank() if d is not None else 0
             res['maps'] = maps_to_host(res['maps']) if rank == 0 else None
+            if self.resid is not None:           # (small, and the same on every rank: host arrays everywhere)
+                res['residuals'] = {k: v.cpu().numpy() for k, v in res['residuals'].items()}
             if self.split is not None:
                 sp = [res['splits']] if self.split_single else res['splits']
                 sp = [maps_to_host(m) if rank == 0 else None for m in sp]
@@ -1317,6 +1530,7 @@ class DeviceDestriper:
         elif d is None or d.get_world_size() == 1:
             x, it, maps = ops.solve_native(threshold, niter)
             split = ops.split_bands
+            m_internal = maps['map']
         else:
             # COMAP_DS_GRAPH=1: the captured-graph driver (one launch per 16 iterations);
             # default: the eager batched driver (4 native calls and 3 all-reduces per iteration,
@@ -1333,6 +1547,7 @@ class DeviceDestriper:
                                   'using the eager CG driver')
             x, it, h, nnum = solver(ops, allreduce or torch_allreduce, threshold, niter)
             maps = self._finish_maps(ops, x, h, nnum)
+            m_internal = self._map_internal       # the global map on the compacted pixels (_finish_maps)
             it = it[:ops.n_bands]
             x = ops.natural(x)
             split = ops.split_bands
@@ -1340,6 +1555,8 @@ class DeviceDestriper:
             nbl = nb if self.gathered is not None else ops.nb
             maps = {k: self._untile(v, nbl) for k, v in maps.items()}
         extra = {} if self.split is None else {'splits': self._split_maps(x)}
+        if self.resid is not None:
+            extra['residuals'] = self._residuals(x, m_internal)
         if not self.multi:
             maps['map2'] = maps['weight']
             return {'x': x, 'iters': it[0], 'maps': maps, **extra}
@@ -1362,6 +1579,7 @@ class DeviceDestriper:
         maps = {'map': ops.zeros(n), 'naive': ops.zeros(n), 'weight': h, 'hits': hits}
         ops.div_map(num, h, maps['map'])
         ops.div_map(nnum, h, maps['naive'])
+        self._map_internal = maps['map'] if self.resid is not None else None    # (the residual pass reads it)
         return {k: self._expand(v) for k, v in maps.items()}
 
     def _solve_ground(self, threshold, niter, to_host):
@@ -1428,7 +1646,8 @@ def maps_to_host(maps):
 
 def run_destriper(_pointing, _tod, _weights, offset_length, pixel_edges, az=None, el=None, ra=None, dec=None,
                   feedid=None, obsids=None, obsid_cuts=None, threshold=1e-6, niter=100, chi2_cutoff=100,
-                  special_weight=None, healpix=False, device=None, map_shape=None, ground=False, split=None):
+                  special_weight=None, healpix=False, device=None, map_shape=None, ground=False, split=None,
+                  residuals=False, residual_cut=None):
     """Destriper.run_destriper (Destriper.py:456-503) on the GPU.
 
     ``pixel_edges[-1] + 1`` is the map size (bin_offset_map, :169).  Returns
@@ -1446,7 +1665,12 @@ def run_destriper(_pointing, _tod, _weights, offset_length, pixel_edges, az=None
     'hits'} entry per feed ('Feed01', ...) or observation ('Obs<obsid>') beside 'All', binned
     from that subset's samples of tod - F x with the solve's own offsets (None maps on ranks
     other than 0; across ranks the names are those of all ranks' feeds / observations), and
-    'offsets', the rank's solved offsets (host, [N/L])."""
+    'offsets', the rank's solved offsets (host, [N/L]).
+    residuals=True and / or residual_cut=c, an extension (``chi2_cutoff`` and ``obsid_cuts`` stay
+    ignored, as in the reference): the residual chi-squared of tod - F x - P m per (observation,
+    feed) and, with a cut, one more solve without the groups above c (DeviceDestriper); the
+    result gains 'Residuals': {'obsids', 'feeds', 'chi2', 'count'[, 'cut', 'chi2_first']}, tables
+    [n_obs, n_feeds], on rank 0 and None on the other ranks.  Not together with ``ground``."""
     if special_weight is not None:
         raise NotImplementedError('special_weight is unused by run_destriper in the reference (:482)')
     import torch
@@ -1457,19 +1681,49 @@ def run_destriper(_pointing, _tod, _weights, offset_length, pixel_edges, az=None
         raise ValueError('ground=True needs az, feedid and obsids')
     if ground and split:
         raise NotImplementedError('split maps with the ground template are not supported')
+    resid = _residual_args(residuals, residual_cut, ground, feedid, obsids)
     specs = split_specs(split, feedid, obsids, offset_length)
     dd = DeviceDestriper(np.asarray(_pointing), np.asarray(_tod, dtype=np.float64),
                          np.asarray(_weights, dtype=np.float64), int(offset_length), npix, device, map_shape=map_shape,
                          ground=(np.asarray(az, dtype=np.float64), feedid, obsids) if ground else None,
-                         split=None if specs is None else [(lab, len(names)) for lab, names in specs])
+                         split=None if specs is None else [(lab, len(names)) for lab, names in specs], **resid)
     res = dd.solve(threshold, niter, to_host=True)
     maps = res['maps']
     if maps is None:                     # a rank other than 0
         maps = {'map': None, 'naive': None, 'weight': None, 'map2': None}
     out = {'All': maps, 'Ground': res['ground']} if ground else {'All': maps}
+    if resid:
+        out['Residuals'] = _residual_table(dd, res['residuals'])
     if specs is not None:
         out.update(_split_entries(specs, res['splits']))
         out['offsets'] = res['x'].cpu().numpy()      # this rank's offsets, which its split maps were binned with
+    return out
+
+
+def _residual_args(residuals, residual_cut, ground, feedid, obsids):
+    """The drivers' ``residuals`` / ``residual_cut`` as DeviceDestriper's keyword arguments
+    ({} when neither is asked for)."""
+    if not residuals and residual_cut is None:
+        return {}
+    if ground:
+        raise NotImplementedError('residuals with the ground template are not supported')
+    if feedid is None or obsids is None:
+        raise ValueError('residuals need feedid and obsids')
+    return {'residuals': True, 'residual_groups': (feedid, obsids), 'residual_cut': residual_cut}
+
+
+def _residual_table(dd, r, band=None):
+    """'Residuals' of a driver's result from res['residuals'] (host arrays; ``band``: of that
+    band of a batched solve): tables [n_obs, n_feeds] on rank 0, None on the other ranks."""
+    d = _dist()
+    if d is not None and d.get_rank() != 0:
+        return None
+    uobs, ufeed = dd.resid_axes
+    out = {'obsids': uobs, 'feeds': ufeed}
+    for k in ('chi2', 'count', 'cut', 'chi2_first'):
+        if k in r:
+            v = np.asarray(r[k])
+            out[k] = (v if band is None else v[band]).reshape(uobs.size, ufeed.size)
     return out
 
 
@@ -1487,7 +1741,8 @@ def _split_entries(specs, splits, band=None):
 
 
 def run_destriper_bands(_pointing, _tods, _weights, offset_length, pixel_edges, keep=None, threshold=1e-6,
-                        niter=100, device=None, map_shape=None, split=None, feedid=None, obsids=None):
+                        niter=100, device=None, map_shape=None, split=None, feedid=None, obsids=None,
+                        residuals=False, residual_cut=None):
     """run_destriper for several sidebands on the same pointing in ONE batched
     device solve (the reference calls run_destriper once per band,
     run_destriper.py:146-189).  _tods/_weights [n_bands, N]; keep [n_bands, N/L]
@@ -1499,7 +1754,9 @@ def run_destriper_bands(_pointing, _tods, _weights, offset_length, pixel_edges, 
     split ('feed', 'obsid' or a list of these, with per-sample ``feedid`` and ``obsids``): each
     band's dict also gets run_destriper's split-map entries, all bands' from one device pass
     per split; a band's 'hits' leave out the offsets it dropped.  With split, ranks other than 0
-    get 'offsets' too (their own), as from run_destriper."""
+    get 'offsets' too (their own), as from run_destriper.
+    residuals / residual_cut: as run_destriper's, every band's table from one device pass and the
+    cut decided per band; each band's dict gains 'Residuals' (None on ranks other than 0)."""
     import torch
     if device is None:
         device = torch.cuda.current_device()
@@ -1507,10 +1764,11 @@ def run_destriper_bands(_pointing, _tods, _weights, offset_length, pixel_edges, 
     tods = np.asarray(_tods, dtype=np.float64)
     if tods.ndim != 2:
         raise ValueError('_tods must be [n_bands, N]')
+    resid = _residual_args(residuals, residual_cut, False, feedid, obsids)
     specs = split_specs(split, feedid, obsids, offset_length)
     dd = DeviceDestriper(np.asarray(_pointing), tods, np.asarray(_weights, dtype=np.float64), int(offset_length), npix,
                          device, keep=None if keep is None else np.asarray(keep, dtype=np.uint8), map_shape=map_shape,
-                         split=None if specs is None else [(lab, len(names)) for lab, names in specs])
+                         split=None if specs is None else [(lab, len(names)) for lab, names in specs], **resid)
     res = dd.solve(threshold, niter, to_host=True)
     d = _dist()
     rank = d.get_rank() if d is not None else 0
@@ -1518,6 +1776,8 @@ def run_destriper_bands(_pointing, _tods, _weights, offset_length, pixel_edges, 
     hm = res['maps']
     for b in range(tods.shape[0]):
         extra = {} if specs is None else _split_entries(specs, res['splits'], band=b)
+        if resid:
+            extra['Residuals'] = _residual_table(dd, res['residuals'], band=b)
         if rank != 0:
             if specs is not None:        # every rank keeps the offsets its split sums were binned with
                 extra['offsets'] = res['x'][b].cpu().numpy()

@@ -126,7 +126,7 @@ def main(filelistname, offset_length=50, feed_weights=None, prefix='fg9', output
          crval=['05:32:00.3', '+12:30:28.0'], crpix=[240, 240], ctype=['RA---CAR', 'DEC--CAR'],
          cdelt=[-0.016666, 0.016666], use_gain_filter=True, calibration=True, calibrator='TauA', threshold=1e-6,
          niter=100, healpix=False, bands=(0, 1, 2, 3), store=None, device=None, batch_bands=True, ground=False,
-         split=None):
+         split=None, residuals=False, residual_cut=None):
     """run_destriper.main (run_destriper.py:79-189).  ``store`` (tests) maps
     filename -> (datasets, attrs) instead of reading files; ``device`` is the
     rank's GPU (default: torch's current device, LOCAL_RANK under torchrun).
@@ -147,7 +147,17 @@ def main(filelistname, offset_length=50, feed_weights=None, prefix='fg9', output
     tod - F x with the solve's offsets (the reference's commented "Create individual feed maps
     too" block, Destriper.py:487-501): each band's dict gains one entry per name and rank 0
     writes <name>_<prefix>_Band<iband>.fits beside All_...; the band's dict also keeps 'offsets',
-    the rank's solved offsets the split maps were binned with.  Not together with ``ground``."""
+    the rank's solved offsets the split maps were binned with.  Not together with ``ground``.
+    ``residuals`` / ``residual_cut`` ([Inputs] residual_chi2 and residual_cut in the .ini; absent =
+    off): the residual chi-squared of tod - F x - P m per (observation, feed) and, with a cut c,
+    one more solve without the (observation, feed) groups whose chi-squared is not <= c
+    (destriper.run_destriper); each band's entry gains 'Residuals' (None on ranks other than 0)
+    and rank 0 writes <output_dir>/<prefix>_residuals_band<iband>.npz.  ``chi2_cutoff`` and
+    ``obsid_cuts`` stay ignored, as in the reference.  Not together with ``ground``."""
+    if ground and (residuals or residual_cut is not None):
+        raise NotImplementedError('residual_chi2 / residual_cut with ground_template is not supported')
+    resid = bool(residuals) or residual_cut is not None
+    rkw = dict(residuals=bool(residuals), residual_cut=residual_cut) if resid else {}
     if split is not None and isinstance(split, str):
         split = [split]
     if split and ground:
@@ -183,14 +193,18 @@ def main(filelistname, offset_length=50, feed_weights=None, prefix='fg9', output
         res = run_destriper_bands(r['pointing'], r['tod'], r['weights'], offset_length, pixel_edges, keep=r['keep'],
                                   threshold=threshold, niter=niter, device=device,
                                   map_shape=None if healpix else (nypix, nxpix), split=split or None,
-                                  feedid=r['feedid'], obsids=r['obsids'])
+                                  feedid=r['feedid'], obsids=r['obsids'], **rkw)
         for iband, maps in zip(bands, res):
-            sky = {k: v for k, v in maps.items() if k not in ('iters', 'offsets')}    # 'All' and the split maps
+            sky = {k: v for k, v in maps.items() if k not in ('iters', 'offsets', 'Residuals')}    # 'All' and the split maps
             if rank == 0:
                 if healpix:
                     write_map_healpix(prefix, sky, r['remapping_array'], map_info, output_dir, iband)
                 else:
                     write_map(prefix, sky, map_info, output_dir, iband)
+                if resid:
+                    _write_residuals(output_dir, prefix, iband, maps['Residuals'])
+            if resid:
+                sky = dict(sky, Residuals=maps['Residuals'])
             # (with split maps the band's entry keeps the offsets they were binned with)
             out[iband] = dict(sky, offsets=maps['offsets']) if split else sky       # (on every rank, as per band)
         return out
@@ -203,8 +217,8 @@ def main(filelistname, offset_length=50, feed_weights=None, prefix='fg9', output
         maps = run_destriper(pointing, tod, weights, offset_length, pixel_edges, az, el, ra, dec, feedid, obsids,
                              obsid_cuts, threshold=threshold, niter=niter, chi2_cutoff=20,
                              device=device, map_shape=None if healpix else (nypix, nxpix), ground=ground,
-                             split=split or None)
-        sky = {k: v for k, v in maps.items() if k not in ('Ground', 'offsets')}    # (the writers iterate the dict: the maps only)
+                             split=split or None, **rkw)
+        sky = {k: v for k, v in maps.items() if k not in ('Ground', 'offsets', 'Residuals')}    # (the writers iterate the dict: the maps only)
         if rank == 0:
             if healpix:
                 write_map_healpix(prefix, sky, remap, map_info, output_dir, iband)
@@ -213,8 +227,30 @@ def main(filelistname, offset_length=50, feed_weights=None, prefix='fg9', output
             if ground:
                 os.makedirs(output_dir, exist_ok=True)
                 np.savez(os.path.join(output_dir, '{}_ground_band{}.npz'.format(prefix, iband)), **maps['Ground'])
+            if resid:
+                _write_residuals(output_dir, prefix, iband, maps['Residuals'])
         out[iband] = maps
     return out
+
+
+def _write_residuals(output_dir, prefix, iband, table):
+    os.makedirs(output_dir, exist_ok=True)
+    np.savez(os.path.join(output_dir, '{}_residuals_band{}.npz'.format(prefix, iband)), **table)
+
+
+def residual_params(params):
+    """(residuals, residual_cut) from the [Inputs] section: ``residual_chi2`` (True / False) and
+    ``residual_cut`` (a number); an absent key, None or False means off."""
+    chi2, cut = params.get('residual_chi2'), params.get('residual_cut')
+    if isinstance(cut, bool) or cut is None:
+        if cut is True:
+            raise ValueError('[Inputs] residual_cut must be a number')
+        cut = None
+    elif not isinstance(cut, float):
+        raise ValueError(f'[Inputs] residual_cut must be a number, not {cut!r}')
+    if not (chi2 is None or isinstance(chi2, bool)):
+        raise ValueError(f'[Inputs] residual_chi2 must be True or False, not {chi2!r}')
+    return bool(chi2), cut
 
 
 def cli(argv):
@@ -226,6 +262,7 @@ def cli(argv):
     feeds = [int(f) for f in (feeds if isinstance(feeds, list) else [feeds])]
     as_list = lambda v: v if isinstance(v, list) else [v]  # noqa: E731
     split = params.get('split_maps')             # 'feed', 'obsid' or both (a list); absent or None: no split maps
+    residuals, residual_cut = residual_params(params)
     return main(params['filelistname'], offset_length=int(params['offset_length']), prefix=params['prefix'],
                 output_dir=params['output_dir'], feeds=feeds, feed_weights=params['feed_weights'],
                 nxpix=int(params['nxpix']), nypix=int(params['nypix']), crval=as_list(params['crval']),
@@ -234,4 +271,5 @@ def cli(argv):
                 calibrator=p['ReadData']['calibrator'], threshold=10 ** float(params['threshold']),
                 niter=int(params['niter']), healpix=params['healpix'],
                 ground=bool(params.get('ground_template', False)),
-                split=[str(k) for k in as_list(split)] if split else None)
+                split=[str(k) for k in as_list(split)] if split else None, residuals=residuals,
+                residual_cut=residual_cut)

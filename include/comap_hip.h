@@ -480,6 +480,35 @@ int comap_destripe_split_maps(comap_ctx *ctx, const int32_t *pixels_dev, const d
 int comap_destripe_split_div(comap_ctx *ctx, const double *num_dev, const double *naive_num_dev,
                              const double *weight_dev, int64_t n, double *map_dev, double *naive_dev);
 
+/* ------------------------------------------------------------ residual chi-squared (an extension) */
+/* How well tod - F x - P m matches the claimed weights, per offset and per group of offsets.
+ * Sample t of offset o = t / L, band b, is counted when pixels[t] >= 0, weights[b][t] > 0 and
+ * (keep_dev == NULL or keep[b][o] != 0); its term is (w r) r with r = (tod[b][t] - x[o][b]) -
+ * map[pixels[t]][b], each operation rounded to f64 on its own.  An uncounted sample contributes
+ * nothing: a negative pixel id has no map value of its own (the CG's wrap read m[npix + p] is not
+ * used here).  A non-finite tod of a counted sample makes its sums NaN.
+ *   off_cnt[o][b]  counted samples of offset o
+ *   off_sum[o][b]  the sum of the offset's L terms (+0.0 for an uncounted sample) in the lane-tree order
+ *   grp_sum[g][b]  the lane-tree sum of off_sum[o][b] over the offsets with group[o] == g, in increasing o
+ *   grp_cnt[g][b]  the integer sum of their counts
+ * Lane-tree order of v[0 .. n): lane l of 64 adds v[l], v[l + 64], ... in that order from +0.0;
+ * then for s = 32, 16, 8, 4, 2, 1: a[l] = a[l] + a[l ^ s]; the result is lane 0's
+ * (mapmaking/destriper.py: lane_tree_sum).  It does not depend on the launch shape; no
+ * floating-point atomics; two calls give the same bytes.
+ * pixels as the problem holds them, tod / weights [n_bands][N], keep [n_bands][N / L] or NULL,
+ * x [N / L][n_bands] in the caller's offset order, map [npix][n_bands] in the pixel order of
+ * `pixels`; group_dev [N / L] in [-1, n_groups) (-1: in no group), or NULL with n_groups 0: no group
+ * stage (grp_* may then be NULL).  off_* [N / L][n_bands] and grp_* [n_groups][n_bands] are written
+ * in full (a group without offsets: 0 and 0).  n_bands in {1, 2, 4}; N < 2^31.
+ * Returns -3 for a pixel id outside [-npix, npix) (read as unbinned, never out of bounds), -4 for
+ * a label outside [-1, n_groups), -1 for null or misshapen arguments.  Synchronises once (segment
+ * count and error flags). */
+int comap_destripe_residuals(comap_ctx *ctx, const int32_t *pixels_dev, const double *tod_dev,
+                             const double *weights_dev, const uint8_t *keep_dev, const double *x_dev,
+                             const double *map_dev, const int32_t *group_dev, int32_t n_groups, int64_t n_samples,
+                             int32_t offset_length, int64_t npix, int32_t n_bands, double *off_sum_dev,
+                             int32_t *off_cnt_dev, double *grp_sum_dev, int64_t *grp_cnt_dev);
+
 /* ------------------------------------------------------------ destriper data prep (COMAPData.py) */
 /* One Level-2 file's inputs to comap_prep_gather (device pointers).  Output row r
  * (0 <= r < n_rows = len(output_feed_index)) takes its tod / weights / az / el /
