@@ -41,7 +41,6 @@
 // kernel adds each group's partials in chunk order.  No floating-point atomics anywhere.
 #include "destriper_internal.h"
 
-#include <hipcub/hipcub.hpp>
 #include <rocprim/device/device_radix_sort.hpp>
 
 struct comap_ground {
@@ -99,13 +98,6 @@ __device__ __forceinline__ int64_t lb32(const int32_t *a, int64_t n, int64_t v)
         if (a[m] < v) lo = m + 1; else hi = m;
     }
     return lo;
-}
-
-inline int bits_for(uint64_t bound)   // bits that hold every key in [0, bound)
-{
-    int b = 1;
-    while (b < 64 && (uint64_t(1) << b) < bound) ++b;
-    return b;
 }
 
 // fixed-order block sum (256 threads): wave sums, then the four waves' sums
@@ -254,8 +246,7 @@ __global__ void k_gr_rms(const double *__restrict__ sum, const double *__restric
 // one its projection reads through the wrap.  flag[0]: a group id outside [0, K); flag[1]: a
 // pixel id outside [-npix, npix).
 __global__ void k_gr_keys(const int32_t *__restrict__ pix, const int32_t *__restrict__ gid, int64_t N, int L,
-                          int64_t npix, int64_t K, uint64_t *__restrict__ key, int32_t *__restrict__ val,
-                          int32_t *__restrict__ flag)
+                          int64_t npix, int64_t K, uint64_t *__restrict__ key, int32_t *__restrict__ flag)
 {
     for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < N; t += (int64_t)gridDim.x * blockDim.x) {
         int64_t k = gid[t / L];
@@ -264,20 +255,7 @@ __global__ void k_gr_keys(const int32_t *__restrict__ pix, const int32_t *__rest
         if (p >= npix || p < -npix) { flag[1] = 1; p = 0; }
         const int64_t q = p >= 0 ? p : npix + p;
         key[t] = (((uint64_t)k * (uint64_t)npix + (uint64_t)q) << 1) | (p < 0 ? 1u : 0u);
-        val[t] = (int32_t)t;
     }
-}
-
-__global__ void k_gr_heads(const uint64_t *__restrict__ skey, int64_t N, uint8_t *__restrict__ head)
-{
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x)
-        head[i] = (i == 0 || skey[i] != skey[i - 1]) ? 1 : 0;
-}
-
-// first read-back in one piece: entries, flags
-__global__ void k_gr_sizes(const int64_t *__restrict__ ne, const int32_t *__restrict__ flag, int64_t *__restrict__ out)
-{
-    if (threadIdx.x == 0) { out[0] = ne[0]; out[1] = flag[0]; out[2] = flag[1]; }
 }
 
 // Entry e = the sorted samples [estart[e], estart[e + 1]): its group, pixel id (negative for an
@@ -642,38 +620,25 @@ int ground_build(comap_ground *g, const int32_t *pix, const double *az, const do
 
     DevTemps tmp(st);
     const int64_t nmax = std::max<int64_t>(N, std::max<int64_t>(NO, K + 1));
-    uint64_t *key = nullptr, *skey = nullptr;
-    int32_t *val = nullptr, *sval = nullptr, *estart = nullptr, *gs = nullptr, *flag = nullptr;
-    uint8_t *head = nullptr;
+    uint64_t *key = nullptr;
+    int32_t *val = nullptr, *gs = nullptr, *flag = nullptr;
     double *ov = nullptr, *gv = nullptr;
-    int64_t *grow = nullptr, *garow = nullptr, *cnt = nullptr;
+    int64_t *grow = nullptr, *garow = nullptr;
     COMAP_CHECK(ctx, tmp.alloc(&key, N));
-    COMAP_CHECK(ctx, tmp.alloc(&skey, N));
     COMAP_CHECK(ctx, tmp.alloc(&val, nmax));
-    COMAP_CHECK(ctx, tmp.alloc(&sval, nmax));
-    COMAP_CHECK(ctx, tmp.alloc(&estart, N));
     COMAP_CHECK(ctx, tmp.alloc(&gs, NO));
     COMAP_CHECK(ctx, tmp.alloc(&flag, 2));
-    COMAP_CHECK(ctx, tmp.alloc(&head, N));
     COMAP_CHECK(ctx, tmp.alloc(&ov, 3 * NO));
     COMAP_CHECK(ctx, tmp.alloc(&gv, 3 * K));
     COMAP_CHECK(ctx, tmp.alloc(&grow, K + 1));
     COMAP_CHECK(ctx, tmp.alloc(&garow, K + 1));
-    COMAP_CHECK(ctx, tmp.alloc(&cnt, 4));
     const int kbits = bits_for((uint64_t)K), pbits = bits_for((uint64_t)npix + 1);
     const int sbits = bits_for((uint64_t)K * (uint64_t)npix * 2u);
-    // sort scratch: the largest of the three sorts (the last one's size is bounded by N) and the select
+    // sort scratch of steps 1 and 4 (the latter's size is bounded by N); step 3's is the helper's own
     size_t tb = 0, b1 = 0;
-    COMAP_CHECK(ctx, rocprim::radix_sort_pairs(nullptr, b1, key, skey, val, sval, (size_t)N, 0u, (unsigned)sbits, st));
+    COMAP_CHECK(ctx, rocprim::radix_sort_pairs(nullptr, b1, val, gs, val, gs, (size_t)NO, 0u, (unsigned)kbits, st));
     tb = std::max(tb, b1);
-    COMAP_CHECK(ctx, rocprim::radix_sort_pairs(nullptr, b1, val, sval, val, sval, (size_t)NO, 0u, (unsigned)kbits, st));
-    tb = std::max(tb, b1);
-    COMAP_CHECK(ctx, rocprim::radix_sort_pairs(nullptr, b1, val, sval, val, sval, (size_t)N, 0u, (unsigned)pbits, st));
-    tb = std::max(tb, b1);
-    COMAP_CHECK(ctx, rocprim::radix_sort_pairs(nullptr, b1, val, sval, val, sval, (size_t)nmax, 0u, 32u, st));
-    tb = std::max(tb, b1);
-    hipcub::CountingInputIterator<int32_t> iota(0);
-    COMAP_CHECK(ctx, hipcub::DeviceSelect::Flagged(nullptr, b1, iota, head, estart, cnt, (int)N, st));
+    COMAP_CHECK(ctx, rocprim::radix_sort_pairs(nullptr, b1, val, val, val, val, (size_t)N, 0u, (unsigned)pbits, st));
     tb = std::max(tb, b1);
     char *cub = nullptr;
     COMAP_CHECK(ctx, tmp.alloc(&cub, tb));
@@ -713,22 +678,14 @@ int ground_build(comap_ground *g, const int32_t *pix, const double *az, const do
     COMAP_LAUNCH_CHECK(ctx);
 
     // ---- 3. the samples sorted by (group, read pixel, off-map); one entry per distinct key
-    k_gr_keys<<<grid_for(N, 65536), 256, 0, st>>>(pix, gid, N, L, npix, K, key, val, flag);
+    // (ds_sorted_segments, destriper_segments.hip: read-back 1 -- entries, flags)
+    k_gr_keys<<<grid_for(N, 65536), 256, 0, st>>>(pix, gid, N, L, npix, K, key, flag);
     COMAP_LAUNCH_CHECK(ctx);
-    b1 = tb;
-    COMAP_CHECK(ctx, rocprim::radix_sort_pairs(cub, b1, key, skey, val, sval, (size_t)N, 0u, (unsigned)sbits, st));
-    k_gr_heads<<<grid_for(N, 65536), 256, 0, st>>>(skey, N, head);
-    COMAP_LAUNCH_CHECK(ctx);
-    b1 = tb;
-    COMAP_CHECK(ctx, hipcub::DeviceSelect::Flagged(cub, b1, iota, head, estart, cnt, (int)N, st));
-    k_gr_sizes<<<1, 64, 0, st>>>(cnt, flag, cnt + 1);
-    COMAP_LAUNCH_CHECK(ctx);
-    int64_t hw[3] = {0, 0, 0};
-    COMAP_CHECK(ctx, hipMemcpyAsync(hw, cnt + 1, sizeof(hw), hipMemcpyDeviceToHost, st));
-    COMAP_CHECK(ctx, hipStreamSynchronize(st));
-    if (hw[1]) return comap_fail(ctx, -3, "ground group id out of range (valid: 0 .. n_groups - 1)");
-    if (hw[2]) return comap_fail(ctx, -3, "pixel index out of range for the map (>= npix or < -npix)");
-    const int64_t ne = hw[0];
+    ds_segments<uint64_t> seg;
+    if (const int src = ds_sorted_segments(ctx, tmp, key, N, sbits, flag, &seg)) return src;
+    if (seg.flag[0]) return comap_fail(ctx, -3, "ground group id out of range (valid: 0 .. n_groups - 1)");
+    if (seg.flag[1]) return comap_fail(ctx, -3, "pixel index out of range for the map (>= npix or < -npix)");
+    const int64_t ne = seg.ne;
     if (ne < 1 || ne > N) return comap_fail(ctx, -2, "ground set-up: bad entry count");
     g->nnz = ne;
 
@@ -742,12 +699,12 @@ int ground_build(comap_ground *g, const int32_t *pix, const double *az, const do
     COMAP_CHECK(ctx, tmp.alloc(&egrp, ne));
     COMAP_CHECK(ctx, tmp.alloc(&pkey, ne));
     COMAP_CHECK(ctx, tmp.alloc(&spkey, ne));
-    // (val / sval are free again: the pixel-major sort's values)
-    k_gr_entries<<<grid_for(ne, 65536), 256, 0, st>>>(skey, sval, estart, ne, N, npix, az, w, g->mu, g->sigma,
+    // (val is free again: the pixel-major sort's values)
+    k_gr_entries<<<grid_for(ne, 65536), 256, 0, st>>>(seg.skey, seg.sval, seg.estart, ne, N, npix, az, w, g->mu, g->sigma,
                                                       g->wrapped, egrp, g->gpix, g->ga, pkey, val);
     k_gr_rowptr<<<grid_for(K + 1), 256, 0, st>>>(egrp, ne, K, garow);
     COMAP_LAUNCH_CHECK(ctx);
-    int32_t *spval = estart;               // (the segment starts are consumed)
+    int32_t *spval = seg.estart;           // (the segment starts are consumed)
     COMAP_CHECK(ctx, rocprim::radix_sort_pairs(nullptr, b1, pkey, spkey, val, spval, (size_t)ne, 0u, (unsigned)pbits, st));
     if (b1 > tb) {
         tb = b1;

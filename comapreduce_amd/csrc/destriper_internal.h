@@ -1,6 +1,8 @@
 // destriper_internal.h -- what the destriper's translation units share: the problem (struct
 // comap_destriper), constants, launch helpers and device helpers of destriper_setup.hip (operator
-// set-up), destriper_cg.hip (CG kernels, solve loop, accessors) and destriper_keys.hip (relabel keys).
+// set-up), destriper_cg.hip (CG kernels, solve loop, accessors) and destriper_keys.hip (relabel keys),
+// and the sorted-segments helper of destriper_segments.hip that destriper_ground.hip (ground set-up),
+// destriper_split.hip (split maps) and destriper_resid.hip (residual group stage) sum by.
 //
 // Destriping map-maker (reference MapMaking/Destriper.py:85-263, 402-503).
 //
@@ -353,6 +355,29 @@ void ds_dot(comap_destriper *d, hipStream_t st, const double *a, const double *b
 void ds_dot_part(comap_destriper *d, hipStream_t st, const double *a, const double *b, int64_t n);
 unsigned ds_upd_grid(int64_t NO);
 void ds_div_map(hipStream_t st, const double *num, const double *h, int64_t n, double *out);
+
+inline int bits_for(uint64_t bound)   // bits that hold every key in [0, bound)
+{
+    int b = 1;
+    while (b < 64 && (uint64_t(1) << b) < bound) ++b;
+    return b;
+}
+
+// Sorted segments (destriper_segments.hip): the n caller-made keys (Key = uint32_t or uint64_t)
+// sorted stably over `bits` bits with their indices, cut into ne segments of equal key -- segment e
+// is the sorted positions [estart[e], estart[e + 1]), n behind the last -- and the caller's two
+// device flag words, read back with the segment count in the call's one host wait.  The buffers
+// come from the caller's DevTemps and live as long as it does.
+template <typename Key>
+struct ds_segments {
+    Key *skey = nullptr;                          // [n] sorted keys
+    int32_t *sval = nullptr, *estart = nullptr;   // [n] sorted indices, [ne] segment starts
+    int64_t ne = 0;
+    int64_t flag[2] = {0, 0};
+};
+template <typename Key>
+int ds_sorted_segments(comap_ctx *ctx, DevTemps &tmp, const Key *key, int64_t n, int bits, const int32_t *flag,
+                       ds_segments<Key> *out);
 
 // a problem's persistent buffers come from the cached device pool (comap_tmp_alloc) in
 // the context stream's order; comap_destripe_destroy returns them after a device sync

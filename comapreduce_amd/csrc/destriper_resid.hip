@@ -29,13 +29,10 @@
 // one by one; a longer offset is walked kRsU rounds (256 samples) at a time.  The butterfly is
 // wave_sum / wave_sum_scatter (all bands' sums in one reduce-scatter; the same tree: a + b == b +
 // a bit for bit), the counts come from the wave's ballot.
-// Group stage: ONE stable radix sort of the N / L (group, offset) pairs (label -1 behind the
-// sentinel G), segment heads, one wave per segment.
+// Group stage: the N / L offsets keyed by their group (label -1 behind the sentinel G), sorted and
+// cut into segments (ds_sorted_segments, destriper_segments.hip), one wave per segment.
 // It needs no comap_destriper: the inputs are the caller's arrays, x in the caller's order.
 #include "destriper_internal.h"
-
-#include <hipcub/hipcub.hpp>
-#include <rocprim/device/device_radix_sort.hpp>
 
 // every product below is rounded before it is added (hipcc contracts a * b + c by default)
 #pragma clang fp contract(off)
@@ -43,13 +40,6 @@
 namespace {
 
 constexpr int kRsU = 4;   // rounds of loads a wave issues before it adds them: offsets (L <= 64) or rounds of one
-
-inline int rs_bits_for(uint64_t bound)   // bits that hold every key in [0, bound)
-{
-    int b = 1;
-    while (b < 64 && (uint64_t(1) << b) < bound) ++b;
-    return b;
-}
 
 // One sample as a lane holds it between its loads and its use.  p < 0: not binned (or no sample).
 template <int NB>
@@ -191,29 +181,16 @@ __global__ void __launch_bounds__(256) k_rs_offsets(const int32_t *__restrict__ 
     }
 }
 
-// key[o] = the offset's group, or the sentinel G for label -1 (in no group); val[o] = o.
+// key[o] = the offset's group, or the sentinel G for label -1 (in no group).
 // flag[1]: a label outside [-1, G).
 __global__ void k_rs_keys(const int32_t *__restrict__ group, int64_t NO, int64_t G, uint32_t *__restrict__ key,
-                          int32_t *__restrict__ val, int32_t *__restrict__ flag)
+                          int32_t *__restrict__ flag)
 {
     for (int64_t o = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; o < NO; o += (int64_t)gridDim.x * blockDim.x) {
         int64_t g = group[o];
         if (g < -1 || g >= G) { flag[1] = 1; g = -1; }
         key[o] = g < 0 ? (uint32_t)G : (uint32_t)g;
-        val[o] = (int32_t)o;
     }
-}
-
-__global__ void k_rs_heads(const uint32_t *__restrict__ skey, int64_t NO, uint8_t *__restrict__ head)
-{
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < NO; i += (int64_t)gridDim.x * blockDim.x)
-        head[i] = (i == 0 || skey[i] != skey[i - 1]) ? 1 : 0;
-}
-
-// the read-back in one piece: segments (0 without a group stage), flags
-__global__ void k_rs_sizes(const int64_t *__restrict__ ne, const int32_t *__restrict__ flag, int64_t *__restrict__ out)
-{
-    if (threadIdx.x == 0) { out[0] = ne ? ne[0] : 0; out[1] = flag[0]; out[2] = flag[1]; }
 }
 
 // One wave per segment e = the sorted offsets [estart[e], estart[e + 1]) of one group, in
@@ -298,9 +275,7 @@ extern "C" int comap_destripe_residuals(comap_ctx *ctx, const int32_t *pix, cons
 
     DevTemps tmp(st, false);    // freed behind the stream's work: the read-back below is the only host wait
     int32_t *flag = nullptr;
-    int64_t *cnt = nullptr;
     COMAP_CHECK(ctx, tmp.alloc(&flag, 2));
-    COMAP_CHECK(ctx, tmp.alloc(&cnt, 4));
     COMAP_CHECK(ctx, hipMemsetAsync(flag, 0, 8, st));
     {
         // 4 waves per block; a wave takes kRsU offsets (L <= 64) or one per turn
@@ -310,46 +285,28 @@ extern "C" int comap_destripe_residuals(comap_ctx *ctx, const int32_t *pix, cons
                                                                          npix, off_sum, off_cnt, flag));
         COMAP_LAUNCH_CHECK(ctx);
     }
-    uint32_t *key = nullptr, *skey = nullptr;
-    int32_t *val = nullptr, *sval = nullptr, *estart = nullptr;
-    uint8_t *head = nullptr;
-    char *cub = nullptr;
+    ds_segments<uint32_t> seg;
     if (groups) {
+        uint32_t *key = nullptr;
         COMAP_CHECK(ctx, tmp.alloc(&key, NO));
-        COMAP_CHECK(ctx, tmp.alloc(&skey, NO));
-        COMAP_CHECK(ctx, tmp.alloc(&val, NO));
-        COMAP_CHECK(ctx, tmp.alloc(&sval, NO));
-        COMAP_CHECK(ctx, tmp.alloc(&estart, NO));
-        COMAP_CHECK(ctx, tmp.alloc(&head, NO));
-        const int sbits = rs_bits_for((uint64_t)G + 1);
-        size_t tb = 0, b1 = 0;
-        COMAP_CHECK(ctx, rocprim::radix_sort_pairs(nullptr, tb, key, skey, val, sval, (size_t)NO, 0u, (unsigned)sbits, st));
-        hipcub::CountingInputIterator<int32_t> iota(0);
-        COMAP_CHECK(ctx, hipcub::DeviceSelect::Flagged(nullptr, b1, iota, head, estart, cnt, (int)NO, st));
-        tb = std::max(tb, b1);
-        COMAP_CHECK(ctx, tmp.alloc(&cub, tb));
-        k_rs_keys<<<grid_for(NO, 65536), 256, 0, st>>>(group, NO, G, key, val, flag);
+        k_rs_keys<<<grid_for(NO, 65536), 256, 0, st>>>(group, NO, G, key, flag);
         COMAP_LAUNCH_CHECK(ctx);
-        b1 = tb;
-        COMAP_CHECK(ctx, rocprim::radix_sort_pairs(cub, b1, key, skey, val, sval, (size_t)NO, 0u, (unsigned)sbits, st));
-        k_rs_heads<<<grid_for(NO, 65536), 256, 0, st>>>(skey, NO, head);
-        COMAP_LAUNCH_CHECK(ctx);
-        b1 = tb;
-        COMAP_CHECK(ctx, hipcub::DeviceSelect::Flagged(cub, b1, iota, head, estart, cnt, (int)NO, st));
+        if (const int rc = ds_sorted_segments(ctx, tmp, key, NO, bits_for((uint64_t)G + 1), flag, &seg)) return rc;
+    } else {
+        // no group stage: the pixel flag alone, still one host wait
+        int32_t hf[2] = {0, 0};
+        COMAP_CHECK(ctx, hipMemcpyAsync(hf, flag, sizeof(hf), hipMemcpyDeviceToHost, st));
+        COMAP_CHECK(ctx, hipStreamSynchronize(st));
+        seg.flag[0] = hf[0];
     }
-    k_rs_sizes<<<1, 64, 0, st>>>(groups ? cnt : nullptr, flag, cnt + 1);
-    COMAP_LAUNCH_CHECK(ctx);
-    int64_t hw[3] = {0, 0, 0};
-    COMAP_CHECK(ctx, hipMemcpyAsync(hw, cnt + 1, sizeof(hw), hipMemcpyDeviceToHost, st));
-    COMAP_CHECK(ctx, hipStreamSynchronize(st));
-    if (hw[1]) return comap_fail(ctx, -3, "pixel index out of range for the map (>= npix or < -npix)");
-    if (hw[2]) return comap_fail(ctx, -4, "residuals: group label out of range (valid: -1 .. n_groups - 1)");
+    if (seg.flag[0]) return comap_fail(ctx, -3, "pixel index out of range for the map (>= npix or < -npix)");
+    if (seg.flag[1]) return comap_fail(ctx, -4, "residuals: group label out of range (valid: -1 .. n_groups - 1)");
     if (!groups) return 0;
-    const int64_t ne = hw[0];
+    const int64_t ne = seg.ne;
     if (ne < 1 || ne > NO) return comap_fail(ctx, -2, "residuals: bad segment count");
     const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((ne + 3) / 4, 65536));
-    COMAP_NB_SWITCH(n_bands, k_rs_groups<NB><<<grid, 256, 0, st>>>(skey, sval, estart, ne, NO, (uint32_t)G, off_sum,
-                                                                    off_cnt, grp_sum, grp_cnt));
+    COMAP_NB_SWITCH(n_bands, k_rs_groups<NB><<<grid, 256, 0, st>>>(seg.skey, seg.sval, seg.estart, ne, NO, (uint32_t)G,
+                                                                    off_sum, off_cnt, grp_sum, grp_cnt));
     COMAP_LAUNCH_CHECK(ctx);
     return 0;
 }

@@ -10,8 +10,8 @@
 // bit.  Negative pixel ids are never binned; label -1 leaves an offset out of every split.
 //
 // One pass for all labels: the samples are keyed with label npix + pixel (a sentinel behind every
-// row for an unbinned sample), sorted with ONE stable radix sort of (key, t) over the bits G npix
-// needs, cut into segments of equal key, and each (segment, band) pair is summed by one lane in
+// row for an unbinned sample), sorted and cut into segments of equal key over the bits G npix needs
+// (ds_sorted_segments, destriper_segments.hip), and each (segment, band) pair is summed by one lane in
 // sorted order -- which is sample order, the sort being stable -- and stored to its slot of the
 // [G][npix][nb] outputs, zeroed beforehand.  No floating-point atomics: two calls agree bit for
 // bit.  A long row is a serial chain by the definition of the order; a lane keeps kSplitU samples'
@@ -20,9 +20,6 @@
 //
 // It needs no comap_destriper: the inputs are the caller's arrays and x in the caller's order.
 #include "destriper_internal.h"
-
-#include <hipcub/hipcub.hpp>
-#include <rocprim/device/device_radix_sort.hpp>
 
 // every product below is rounded before it is added (hipcc contracts a * b + c by default, and its
 // __dmul_rn / __dadd_rn are plain operators that contract too)
@@ -34,19 +31,10 @@ constexpr int kSplitU = 8;   // samples whose loads a summing lane issues before
 constexpr int64_t kSplitLong = 512;   // a row from this many samples on is a long row
 constexpr int kSplitWaveRows = 8;     // a wave sums its long rows together when it holds at most this many
 
-inline int split_bits_for(uint64_t bound)   // bits that hold every key in [0, bound)
-{
-    int b = 1;
-    while (b < 64 && (uint64_t(1) << b) < bound) ++b;
-    return b;
-}
-
 // key[t] = label npix + pixel, or the sentinel G npix for a sample no split bins (negative pixel
-// id, label -1); val[t] = t.  flag[0]: a label outside [-1, G); flag[1]: a pixel id outside
-// [-npix, npix).
+// id, label -1).  flag[0]: a label outside [-1, G); flag[1]: a pixel id outside [-npix, npix).
 __global__ void k_sp_keys(const int32_t *__restrict__ pix, const int32_t *__restrict__ label, int64_t N, int L,
-                          int64_t npix, int64_t G, uint32_t *__restrict__ key, int32_t *__restrict__ val,
-                          int32_t *__restrict__ flag)
+                          int64_t npix, int64_t G, uint32_t *__restrict__ key, int32_t *__restrict__ flag)
 {
     const uint32_t sentinel = (uint32_t)(G * npix);
     for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < N; t += (int64_t)gridDim.x * blockDim.x) {
@@ -55,20 +43,7 @@ __global__ void k_sp_keys(const int32_t *__restrict__ pix, const int32_t *__rest
         int64_t p = pix[t];
         if (p >= npix || p < -npix) { flag[1] = 1; p = -1; }
         key[t] = (g < 0 || p < 0) ? sentinel : (uint32_t)(g * npix + p);
-        val[t] = (int32_t)t;
     }
-}
-
-__global__ void k_sp_heads(const uint32_t *__restrict__ skey, int64_t N, uint8_t *__restrict__ head)
-{
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x)
-        head[i] = (i == 0 || skey[i] != skey[i - 1]) ? 1 : 0;
-}
-
-// the read-back in one piece: segments, flags
-__global__ void k_sp_sizes(const int64_t *__restrict__ ne, const int32_t *__restrict__ flag, int64_t *__restrict__ out)
-{
-    if (threadIdx.x == 0) { out[0] = ne[0]; out[1] = flag[0]; out[2] = flag[1]; }
 }
 
 // One batch of a long row as a wave holds it: lane l has the row's sample i + l -- its weight, its
@@ -252,51 +227,25 @@ extern "C" int comap_destripe_split_maps(comap_ctx *ctx, const int32_t *pix, con
     COMAP_CHECK(ctx, hipMemsetAsync(hits, 0, out_bytes, st));
     if (N == 0) return 0;
 
-    DevTemps tmp(st, false);    // freed behind the stream's work: the read-back below is the only host wait
-    uint32_t *key = nullptr, *skey = nullptr;
-    int32_t *val = nullptr, *sval = nullptr, *estart = nullptr, *flag = nullptr;
-    uint8_t *head = nullptr;
-    int64_t *cnt = nullptr;
-    char *cub = nullptr;
+    DevTemps tmp(st, false);    // freed behind the stream's work: the helper's read-back is the only host wait
+    uint32_t *key = nullptr;
+    int32_t *flag = nullptr;
     COMAP_CHECK(ctx, tmp.alloc(&key, N));
-    COMAP_CHECK(ctx, tmp.alloc(&skey, N));
-    COMAP_CHECK(ctx, tmp.alloc(&val, N));
-    COMAP_CHECK(ctx, tmp.alloc(&sval, N));
-    COMAP_CHECK(ctx, tmp.alloc(&estart, N));
-    COMAP_CHECK(ctx, tmp.alloc(&head, N));
     COMAP_CHECK(ctx, tmp.alloc(&flag, 2));
-    COMAP_CHECK(ctx, tmp.alloc(&cnt, 4));
     const uint32_t sentinel = (uint32_t)(G * npix);
-    const int sbits = split_bits_for((uint64_t)sentinel + 1);
-    size_t tb = 0, b1 = 0;
-    COMAP_CHECK(ctx, rocprim::radix_sort_pairs(nullptr, tb, key, skey, val, sval, (size_t)N, 0u, (unsigned)sbits, st));
-    hipcub::CountingInputIterator<int32_t> iota(0);
-    COMAP_CHECK(ctx, hipcub::DeviceSelect::Flagged(nullptr, b1, iota, head, estart, cnt, (int)N, st));
-    tb = std::max(tb, b1);
-    COMAP_CHECK(ctx, tmp.alloc(&cub, tb));
-
     COMAP_CHECK(ctx, hipMemsetAsync(flag, 0, 8, st));
-    k_sp_keys<<<grid_for(N, 65536), 256, 0, st>>>(pix, label, N, offset_length, npix, G, key, val, flag);
+    k_sp_keys<<<grid_for(N, 65536), 256, 0, st>>>(pix, label, N, offset_length, npix, G, key, flag);
     COMAP_LAUNCH_CHECK(ctx);
-    b1 = tb;
-    COMAP_CHECK(ctx, rocprim::radix_sort_pairs(cub, b1, key, skey, val, sval, (size_t)N, 0u, (unsigned)sbits, st));
-    k_sp_heads<<<grid_for(N, 65536), 256, 0, st>>>(skey, N, head);
-    COMAP_LAUNCH_CHECK(ctx);
-    b1 = tb;
-    COMAP_CHECK(ctx, hipcub::DeviceSelect::Flagged(cub, b1, iota, head, estart, cnt, (int)N, st));
-    k_sp_sizes<<<1, 64, 0, st>>>(cnt, flag, cnt + 1);
-    COMAP_LAUNCH_CHECK(ctx);
-    int64_t hw[3] = {0, 0, 0};
-    COMAP_CHECK(ctx, hipMemcpyAsync(hw, cnt + 1, sizeof(hw), hipMemcpyDeviceToHost, st));
-    COMAP_CHECK(ctx, hipStreamSynchronize(st));
-    if (hw[2]) return comap_fail(ctx, -3, "pixel index out of range for the map (>= npix or < -npix)");
-    if (hw[1]) return comap_fail(ctx, -4, "split maps: label out of range (valid: -1 .. n_labels - 1)");
-    const int64_t ne = hw[0];
+    ds_segments<uint32_t> seg;
+    if (const int rc = ds_sorted_segments(ctx, tmp, key, N, bits_for((uint64_t)sentinel + 1), flag, &seg)) return rc;
+    if (seg.flag[1]) return comap_fail(ctx, -3, "pixel index out of range for the map (>= npix or < -npix)");
+    if (seg.flag[0]) return comap_fail(ctx, -4, "split maps: label out of range (valid: -1 .. n_labels - 1)");
+    const int64_t ne = seg.ne;
     if (ne < 1 || ne > N) return comap_fail(ctx, -2, "split maps: bad segment count");
 
     COMAP_NB_SWITCH(n_bands, k_sp_sum<NB><<<grid_for(ne * NB, 65536), 256, 0, st>>>(
-                                 skey, sval, estart, ne, N, NO, offset_length, sentinel, tod, w, keep, x, num, nnum, wgt,
-                                 hits));
+                                 seg.skey, seg.sval, seg.estart, ne, N, NO, offset_length, sentinel, tod, w, keep, x, num,
+                                 nnum, wgt, hits));
     COMAP_LAUNCH_CHECK(ctx);
     return 0;
 }

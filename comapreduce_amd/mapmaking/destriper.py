@@ -504,13 +504,18 @@ class DeviceOps(_Vectors):
                                                None if self.keep is None else N.dptr(self.keep), self._v(x),
                                                N.dptr(labels), G, self.pix.numel(), self.L, self.npix, self.nb,
                                                *(N.dptr(v) for v in out))
+        self._pass_rc(rc, 'comap_destripe_split_maps', 'split', G)
+        return tuple(out)
+
+    def _pass_rc(self, rc, fn, what, G):
+        """The return code of a post-solve pass (split maps, residuals): -3 is a pixel id out of
+        range (IndexError), -4 a label (ValueError)."""
         if rc == -3:
             raise IndexError(f'pixel index out of range for a map of {self.npix} pixels '
                              f'(valid: -{self.npix} .. {self.npix - 1})')
         if rc == -4:
-            raise ValueError(f'split label out of range (valid: -1 .. {G - 1})')
-        N.check(rc, self.ctx, 'comap_destripe_split_maps')
-        return tuple(out)
+            raise ValueError(f'{what} label out of range (valid: -1 .. {G - 1})')
+        N.check(rc, self.ctx, fn)
 
     def split_div(self, num, nnum, weight):
         """(map, naive) = (num, naive_num) / weight where weight != 0, else the numerator."""
@@ -553,12 +558,7 @@ class DeviceOps(_Vectors):
                                               self.pix.numel(), self.L, self.npix, self.nb, N.dptr(off_sum),
                                               N.dptr(off_cnt), None if group is None else N.dptr(grp_sum),
                                               None if group is None else N.dptr(grp_cnt))
-        if rc == -3:
-            raise IndexError(f'pixel index out of range for a map of {self.npix} pixels '
-                             f'(valid: -{self.npix} .. {self.npix - 1})')
-        if rc == -4:
-            raise ValueError(f'residual group label out of range (valid: -1 .. {G - 1})')
-        N.check(rc, self.ctx, 'comap_destripe_residuals')
+        self._pass_rc(rc, 'comap_destripe_residuals', 'residual group', G)
         return off_sum, off_cnt, grp_sum, grp_cnt
 
     # ---- single-rank native solve (no Python per iteration)
@@ -669,31 +669,13 @@ def merge_ground_tables(tables):
     return out
 
 
-def _ranks_agree(d, error, held=None):
-    """Every rank's set-up status exchanged, so that all ranks raise or none does (a rank
-    that raised alone would leave its peers waiting in the next collective).  error: this
-    rank's exception or None; held: its populated-pair table for merge_ground_tables'
-    duplicate check, which then also fails on every rank."""
-    mine = (None if error is None else (type(error).__name__, str(error)), held)
+def _agree(d, what, error, payload=None):
+    """Every rank's status (``error``: its exception or None) and ``payload`` exchanged in one
+    all_gather_object, so that all ranks raise or none does (a rank that raised alone would leave
+    its peers waiting in the next collective): the failing rank raises its own exception, the
+    others ValueError.  Returns every rank's payload in rank order."""
     everyone = [None] * d.get_world_size()
-    d.all_gather_object(everyone, mine)
-    for rank, (err, _) in enumerate(everyone):
-        if err is not None:
-            if rank == d.get_rank():
-                raise error
-            raise ValueError(f'ground template set-up failed on rank {rank}: {err[0]}: {err[1]}')
-    merge_ground_tables([t for _, t in everyone])
-
-
-SPLIT_KEYS = ('map', 'naive', 'weight', 'hits')
-
-
-def _split_agree(d, error, values=None, what='split maps'):
-    """The split maps' exchange across ranks: every rank's status (``error``: its exception or
-    None), so that all ranks raise or none does, and every rank's ``values`` (its label values,
-    or None), which are returned in rank order."""
-    everyone = [None] * d.get_world_size()
-    d.all_gather_object(everyone, (None if error is None else (type(error).__name__, str(error)), values))
+    d.all_gather_object(everyone, (None if error is None else (type(error).__name__, str(error)), payload))
     for rank, (err, _) in enumerate(everyone):
         if err is not None:
             if rank == d.get_rank():
@@ -702,24 +684,37 @@ def _split_agree(d, error, values=None, what='split maps'):
     return [v for _, v in everyone]
 
 
+def _on_every_rank(what, step, catch=ValueError, payload=None):
+    """(step(), every rank's payload(step()) in rank order) -- the local ``step`` of ``what``
+    ('split maps', 'residuals', ...) under the ranks' rule: on one rank its exception propagates
+    (and the payloads are None); across ranks an exception of the types ``catch`` is held back,
+    exchanged (_agree: one all_gather_object, before the collectives the step protects) and raised
+    on every rank or on none."""
+    d = _dist()
+    if d is None or d.get_world_size() == 1:
+        return step(), None
+    error = result = mine = None
+    try:
+        result = step()
+        mine = None if payload is None else payload(result)
+    except catch as e:
+        error = e
+    return result, _agree(d, what, error, mine)
+
+
+SPLIT_KEYS = ('map', 'naive', 'weight', 'hits')
+
+
 def residual_group_labels(feedid, obsids, offset_length):
     """The residual table's (observation, feed) group of every offset: (gid int32 [N/L],
     unique_obsids, unique_feeds), ``ground_groups``' labels (group = i n_feeds + j; an offset
     that straddles two groups raises ValueError) -- across ranks over the union of all ranks'
     observations and feeds, taken as ``split_specs`` takes its labels, so that group g means the
     same on every rank; a rank's ValueError is raised on every rank."""
-    d = _dist()
-    ranks = d is not None and d.get_world_size() > 1
-    error, mine = None, None
-    try:
-        mine = ground_groups(feedid, obsids, offset_length)
-    except ValueError as e:
-        if not ranks:
-            raise
-        error = e
-    if not ranks:
+    mine, every = _on_every_rank('residuals', lambda: ground_groups(feedid, obsids, offset_length),
+                                 payload=lambda m: (m[1], m[2]))
+    if every is None:
         return mine
-    every = _split_agree(d, error, None if mine is None else (mine[1], mine[2]), what='residuals')
     gid, uobs, ufeed = mine
     aobs = np.unique(np.concatenate([np.asarray(v[0]).reshape(-1) for v in every]))
     afeed = np.unique(np.concatenate([np.asarray(v[1]).reshape(-1) for v in every]))
@@ -777,18 +772,12 @@ def split_specs(split, feedid, obsids, offset_length):
     kinds = [split] if isinstance(split, str) else list(split)
     if feedid is None or obsids is None:
         raise ValueError('split maps need feedid and obsids')
-    d = _dist()
-    ranks = d is not None and d.get_world_size() > 1
-    error, per_offset, values = None, None, None
-    try:
+    def local():
         per_offset = [_offset_values(by, feedid, obsids, offset_length) for by in kinds]
-        values = [np.unique(v) for v in per_offset]
-    except ValueError as e:
-        if not ranks:
-            raise
-        error = e
-    if ranks:
-        every = _split_agree(d, error, values)
+        return per_offset, [np.unique(v) for v in per_offset]
+
+    (per_offset, values), every = _on_every_rank('split maps', local, payload=lambda r: r[1])
+    if every is not None:
         values = [np.concatenate([r[i] for r in every]) for i in range(len(kinds))]
     return [_labels_in(by, v, vals) for by, v, vals in zip(kinds, per_offset, values)]
 
@@ -1110,15 +1099,11 @@ class DeviceDestriper:
             if self.multi:
                 raise NotImplementedError('the ground template solves one band: pass a 1-D tod')
         ranks = d is not None and d.get_world_size() > 1
-        if ground is not None and ranks and os.environ.get('COMAP_DS_RANKS', 'shard') == 'gather':
+        if ranks and os.environ.get('COMAP_DS_RANKS', 'shard') == 'gather':
             import warnings
-            warnings.warn('COMAP_DS_RANKS=gather is not supported with the ground template: sharding')
-        if split is not None and ranks and os.environ.get('COMAP_DS_RANKS', 'shard') == 'gather':
-            import warnings
-            warnings.warn('COMAP_DS_RANKS=gather is not supported with split maps: sharding')
-        if residuals is not None and ranks and os.environ.get('COMAP_DS_RANKS', 'shard') == 'gather':
-            import warnings
-            warnings.warn('COMAP_DS_RANKS=gather is not supported with residuals: sharding')
+            for asked, what in ((ground, 'the ground template'), (split, 'split maps'), (residuals, 'residuals')):
+                if asked is not None:
+                    warnings.warn(f'COMAP_DS_RANKS=gather is not supported with {what}: sharding')
         if ranks:
             if ground is None and split is None and residuals is None \
                     and self._choose_gather(d, pixels, tod, offset_length):
@@ -1133,97 +1118,70 @@ class DeviceDestriper:
                 gid, uobs, ufeed = residual_group_labels(*residual_groups, offset_length)   # (fails on every rank)
                 self.resid_axes = (uobs, ufeed)
                 residuals = (gid, uobs.size * ufeed.size)
-            # (a rank's bad labels must fail every rank, as for the split labels)
-            error = None
-            try:
-                self.resid = self._labels(*residuals, 'residual group')
-            except ValueError as e:
-                if not ranks:
-                    raise
-                error = e
-            if ranks:
-                _split_agree(d, error, what='residuals')
+            # (a rank's bad labels, like any local set-up error below, must fail every rank)
+            self.resid, _ = _on_every_rank('residuals', lambda: self._labels(*residuals, 'residual group'))
         if split is not None:
-            # (a rank's bad labels must fail every rank, as a ground set-up error does)
-            error = None
-            try:
-                self._set_split(split)
-            except ValueError as e:
-                if not ranks:
-                    raise
-                error = e
-            if ranks:
-                _split_agree(d, error)
+            # self.split_single: the caller passed one (labels, n_labels) pair, not a list
+            self.split_single = isinstance(split, tuple)
+            pairs = [split] if self.split_single else split
+            self.split, _ = _on_every_rank('split maps', lambda: [self._labels(*p, 'split', True) for p in pairs])
         if ground is not None:
             az, feedid, obsids = ground
-            # across ranks, a rank that raised here alone would leave its peers in a collective:
-            # its local set-up error is held back and _ranks_agree raises on every rank, or on none
-            error, table = None, None
-            try:
+
+            def set_up():
                 gid, uobs, ufeed = ground_groups(feedid, obsids, offset_length)
+                self.ground = (uobs, ufeed)
                 self.held = (np.bincount(gid, minlength=uobs.size * ufeed.size) > 0).reshape(uobs.size, ufeed.size)
-                table = {'obsids': uobs, 'feeds': ufeed, 'held': self.held}
                 self.gops = N.retry_oom(GroundOps, self.ops, az, gid, uobs.size * ufeed.size)
-            except (ValueError, IndexError) as e:
-                if not ranks:
-                    raise
-                error = e
-            if ranks:
-                _ranks_agree(d, error, table)
-            self.ground = (uobs, ufeed)
+                return {'obsids': uobs, 'feeds': ufeed, 'held': self.held}
 
-    def _set_split(self, split):
-        """self.split = [(int32 CUDA labels [N/L], n_labels)]; self.split_single: the caller
-        passed one pair, not a list.  Host labels are range-checked here, device labels by the
-        pass itself (ValueError either way)."""
+            _, tables = _on_every_rank('ground template set-up', set_up, (ValueError, IndexError), lambda t: t)
+            if tables is not None:
+                merge_ground_tables(tables)     # two ranks holding one (observation, feed) fails on every rank
+
+    def _labels(self, labels, n_labels, what, times_npix=False):
+        """(int32 CUDA labels [N/L], n_labels) of a split ('split') or of the residual groups;
+        host labels are range-checked here, device labels by the pass itself (ValueError either
+        way).  times_npix: n_labels * npix must fit 31 bits too (the split maps' key)."""
         torch = self.ops.torch
-        self.split_single = isinstance(split, tuple)
-        out = []
-        for labels, n_labels in ([split] if self.split_single else split):
-            G = int(n_labels)
-            if not isinstance(labels, torch.Tensor):
-                labels = np.asarray(labels).reshape(-1)
-                if labels.size and (int(labels.max()) >= G or int(labels.min()) < -1):
-                    raise ValueError(f'split label out of range (valid: -1 .. {G - 1})')
-            t = self.ops._t(labels, torch.int32)
-            if t.numel() != self.ops.n_offsets:
-                raise ValueError(f'split labels: one per offset ({self.ops.n_offsets}), not {t.numel()}')
-            if G < 1 or G * self.ops.npix >= 2 ** 31:
-                raise ValueError(f'n_labels * npix must lie in [1, 2^31), not {G} * {self.ops.npix}')
-            out.append((t, G))
-        self.split = out
+        G = int(n_labels)
+        if not isinstance(labels, torch.Tensor):
+            labels = np.asarray(labels).reshape(-1)
+            if labels.size and (int(labels.max()) >= G or int(labels.min()) < -1):
+                raise ValueError(f'{what} label out of range (valid: -1 .. {G - 1})')
+        t = self.ops._t(labels, torch.int32)
+        if t.numel() != self.ops.n_offsets:
+            raise ValueError(f'{what} labels: one per offset ({self.ops.n_offsets}), not {t.numel()}')
+        if times_npix and (G < 1 or G * self.ops.npix >= 2 ** 31):
+            raise ValueError(f'n_labels * npix must lie in [1, 2^31), not {G} * {self.ops.npix}')
+        if G < 1:
+            raise ValueError(f'{what}: n_groups must be >= 1, not {G}')
+        return t, G
 
-    def _split_maps(self, x, to_host=False):
-        """res['splits'] for the solved offsets ``x`` ([N/L * nb], the caller's order): per
-        requested split the rank's sums (DeviceOps.split_maps) added across ranks, divided, and
-        laid out as the maps are: expanded from the compacted pixels, in the caller's pixel
-        order, [n_labels, npix] or [n_bands, n_labels, npix].  to_host: host arrays on rank 0,
-        None on the others."""
+    def _split_maps(self, x):
+        """res['splits'] (device tensors) for the solved offsets ``x`` ([N/L * nb], the caller's
+        order): per requested split the rank's sums (DeviceOps.split_maps) added across ranks,
+        divided, and laid out as the maps are: expanded from the compacted pixels, in the caller's
+        pixel order, [n_labels, npix] or [n_bands, n_labels, npix]."""
         ops = self.ops
-        d = _dist()
-        rank = d.get_rank() if d is not None else 0
-        ranks = d is not None and d.get_world_size() > 1
         out = []
         for labels, G in self.split:
             # (the pass itself checks device labels and pixel ids: across ranks its error must reach
             # every rank before the sums' all-reduce, where the other ranks would wait for this one)
-            error = None
-            try:
-                num, nnum, weight, hits = ops.split_maps(x, labels, G)
-            except (ValueError, IndexError, N.NativeError) as e:
-                if not ranks:
-                    raise
-                error = e
-            if ranks:
-                _split_agree(d, error)
+            (num, nnum, weight, hits), _ = _on_every_rank('split maps', lambda: ops.split_maps(x, labels, G),
+                                                          (ValueError, IndexError, N.NativeError))
             for v in (num, nnum, weight, hits):
                 torch_allreduce(v)
             m, naive = ops.split_div(num, nnum, weight)
-            maps = {k: self._split_layout(v, G) for k, v in zip(SPLIT_KEYS, (m, naive, weight, hits))}
-            if to_host:
-                maps = maps_to_host(maps) if rank == 0 else None
-            out.append(maps)
+            out.append({k: self._split_layout(v, G) for k, v in zip(SPLIT_KEYS, (m, naive, weight, hits))})
         return out[0] if self.split_single else out
+
+    def _splits_to_host(self, splits):
+        """res['splits'] as host arrays on rank 0, None in their place on the other ranks."""
+        d = _dist()
+        rank = d.get_rank() if d is not None else 0
+        sp = [maps_to_host(m) if rank == 0 else None for m in ([splits] if self.split_single else splits)]
+        return sp[0] if self.split_single else sp
 
     def _split_layout(self, v, G):
         """[G * npix_internal * nb] (label, pixel, band fastest) -> [G, npix] (one band) or
@@ -1241,50 +1199,26 @@ class DeviceDestriper:
         return t.permute(2, 0, 1)[:ops.n_bands].contiguous()
 
     # ---- residual chi-squared
-    def _labels(self, labels, n_labels, what):
-        """(int32 CUDA labels [N/L], n_labels); host labels are range-checked here, device labels
-        by the pass itself (ValueError either way)."""
-        torch = self.ops.torch
-        G = int(n_labels)
-        if not isinstance(labels, torch.Tensor):
-            labels = np.asarray(labels).reshape(-1)
-            if labels.size and (int(labels.max()) >= G or int(labels.min()) < -1):
-                raise ValueError(f'{what} label out of range (valid: -1 .. {G - 1})')
-        t = self.ops._t(labels, torch.int32)
-        if t.numel() != self.ops.n_offsets:
-            raise ValueError(f'{what} labels: one per offset ({self.ops.n_offsets}), not {t.numel()}')
-        if G < 1:
-            raise ValueError(f'{what}: n_groups must be >= 1, not {G}')
-        return t, G
+    def _bands(self, v):
+        """[n * nb] interleaved table -> [n] (one band) or [n_bands, n]."""
+        return self.ops.split_bands(v) if self.multi else v.reshape(-1, self.ops.nb)[:, 0].contiguous()
 
     def _residuals(self, x, m):
         """res['residuals'] (device tensors) for the solved offsets ``x`` ([N/L * nb], the caller's
         order) and the global map ``m`` ([npix_internal * nb], before _expand / _untile): the rank's
         pass (DeviceOps.residuals), the group sums and counts added across ranks -- with whole
         files per rank a group has one contributing rank, so the sum is exact."""
-        ops = self.ops
-        torch = ops.torch
-        d = _dist()
-        ranks = d is not None and d.get_world_size() > 1
-        gid, G = self.resid
+        torch = self.ops.torch
         # (the pass itself checks device labels and pixel ids: across ranks its error must reach
         # every rank before the all-reduce, where the other ranks would wait for this one)
-        error = None
-        try:
-            off_sum, off_cnt, grp_sum, grp_cnt = ops.residuals(x, m, gid, G)
-        except (ValueError, IndexError, N.NativeError) as e:
-            if not ranks:
-                raise
-            error = e
-        if ranks:
-            _split_agree(d, error, what='residuals')
-            torch_allreduce(grp_sum)
-            torch_allreduce(grp_cnt)
-        lay = (lambda v: v.reshape(-1, ops.nb).t()[:ops.n_bands].contiguous()) if self.multi \
-            else (lambda v: v.reshape(-1, ops.nb)[:, 0].contiguous())
-        s, c = lay(grp_sum), lay(grp_cnt)
+        (off_sum, off_cnt, grp_sum, grp_cnt), _ = _on_every_rank(
+            'residuals', lambda: self.ops.residuals(x, m, *self.resid), (ValueError, IndexError, N.NativeError))
+        torch_allreduce(grp_sum)
+        torch_allreduce(grp_cnt)
+        s, c = self._bands(grp_sum), self._bands(grp_cnt)
         chi2 = torch.where(c > 0, s / torch.where(c > 0, c, torch.ones_like(c)).to(torch.float64), torch.zeros_like(s))
-        return {'chi2': chi2, 'sum': s, 'count': c, 'offset_sum': lay(off_sum), 'offset_count': lay(off_cnt)}
+        return {'chi2': chi2, 'sum': s, 'count': c, 'offset_sum': self._bands(off_sum),
+                'offset_count': self._bands(off_cnt)}
 
     def _cut_groups(self, cut):
         """The operator rebuilt without the cut groups (``cut`` bool [n_bands, G] or [G]): band
@@ -1511,7 +1445,7 @@ class DeviceDestriper:
             else:
                 res = {'x': ops.split_bands(x), 'iters': it, 'maps': maps}
             if self.split is not None:           # after the overlapped solve, on the device x
-                res['splits'] = self._split_maps(x, to_host=True)
+                res['splits'] = self._splits_to_host(self._split_maps(x))
             return res
         if to_host:
             res = self._solve(threshold, niter, False, None)
@@ -1520,9 +1454,7 @@ class DeviceDestriper:
             if self.resid is not None:           # (small, and the same on every rank: host arrays everywhere)
                 res['residuals'] = {k: v.cpu().numpy() for k, v in res['residuals'].items()}
             if self.split is not None:
-                sp = [res['splits']] if self.split_single else res['splits']
-                sp = [maps_to_host(m) if rank == 0 else None for m in sp]
-                res['splits'] = sp[0] if self.split_single else sp
+                res['splits'] = self._splits_to_host(res['splits'])
             return res
         if self.gathered is not None:
             x, it, maps, nb, nbands = self._solve_gathered(d, threshold, niter)
@@ -1546,8 +1478,7 @@ class DeviceDestriper:
                     warnings.warn(f'COMAP_DS_GRAPH=1 needs the nccl (RCCL) backend, not {d.get_backend()}: '
                                   'using the eager CG driver')
             x, it, h, nnum = solver(ops, allreduce or torch_allreduce, threshold, niter)
-            maps = self._finish_maps(ops, x, h, nnum)
-            m_internal = self._map_internal       # the global map on the compacted pixels (_finish_maps)
+            maps, m_internal = self._finish_maps(ops, x, h, nnum)
             it = it[:ops.n_bands]
             x = ops.natural(x)
             split = ops.split_bands
@@ -1568,7 +1499,8 @@ class DeviceDestriper:
         """The device maps {'map', 'naive', 'weight', 'hits'} of solution ``u`` of operator ``op``
         (self.ops or self.gops: op.bin(u, 1, num) is the rank's naive numerator - W u), from the
         global weight map h and naive numerator nnum: hits and the numerator summed across
-        ranks, divided by h and expanded to the full map."""
+        ranks, divided by h and expanded to the full map; and the map as it is before that, on
+        the problem's internal (compacted) pixels, which the residual pass reads."""
         ops = self.ops
         n = ops.npix * ops.nb
         _, hits, _ = ops.local_maps()
@@ -1579,8 +1511,7 @@ class DeviceDestriper:
         maps = {'map': ops.zeros(n), 'naive': ops.zeros(n), 'weight': h, 'hits': hits}
         ops.div_map(num, h, maps['map'])
         ops.div_map(nnum, h, maps['naive'])
-        self._map_internal = maps['map'] if self.resid is not None else None    # (the residual pass reads it)
-        return {k: self._expand(v) for k, v in maps.items()}
+        return {k: self._expand(v) for k, v in maps.items()}, maps['map']
 
     def _solve_ground(self, threshold, niter, to_host):
         """solve() with the ground template, then the maps from the offsets AND the fitted
@@ -1610,7 +1541,7 @@ class DeviceDestriper:
             raise ValueError("COMAP_DS_GROUND_SOLVE must be 'native', 'eager' or, across ranks, 'batched', "
                              f'not {mode!r}')
         if ranks or mode == 'eager':
-            maps = self._finish_maps(g, u, h, nnum)
+            maps, _ = self._finish_maps(g, u, h, nnum)
         if self.layout is not None:
             maps = {k: self._untile(v, 1) for k, v in maps.items()}
         maps['map2'] = maps['weight']

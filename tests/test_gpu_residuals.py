@@ -132,6 +132,32 @@ def check_c_call():
     assert raw_call(pix[:n1], case['tod'][None, :n1], case['w'][None, :n1], x[:, None], m[:, None], gid, G0, L,
                     npix)[0] == -1
     assert raw_call(*args, gid, G0, L, npix, nb=3)[0] == -1   # (refused before any buffer is touched)
+    check_degenerate_segments()
+
+
+def check_degenerate_segments():
+    """The group stage's segment counts at their smallest (L = 10, 7 pixels, one band, one group):
+    only the sentinel's segment (every offset labelled -1), exactly one live segment, no counted
+    sample at all (every pixel id -2), and a single offset."""
+    L, npix = 10, 7
+    rng = np.random.default_rng(11)
+    for what, NO, pix, label in (('all labelled -1', 3, None, -1), ('one pixel', 3, 4, 0), ('every pixel -2', 3, -2, 0),
+                                 ('one offset', 1, None, 0)):
+        n = NO * L
+        p = rng.integers(0, npix, n).astype(np.int32) if pix is None else np.full(n, pix, np.int32)
+        tod, w, x, m = rng.standard_normal(n), rng.uniform(0.5, 2.0, n), rng.standard_normal(NO), rng.standard_normal(npix)
+        gid = np.full(NO, label, np.int32)
+        want = restate(p, tod, w, x, m, L, gid, 1)
+        rc, got, msg = raw_call(p, tod[None], w[None], x[:, None], m[:, None], gid, 1, L, npix)
+        assert rc == 0, (what, msg)
+        same([v[:, 0] for v in got], want, what)
+        if label < 0:
+            assert got[2][0, 0] == 0.0 and not np.signbit(got[2][0, 0]) and got[3][0, 0] == 0, what
+            assert got[1].sum() == n and np.all(got[0] > 0), what
+        elif pix == -2:
+            assert not got[0].any() and not got[1].any() and not got[2].any() and not got[3].any(), what
+        else:
+            assert got[3][0, 0] == n and got[2][0, 0] > 0, what
 
 
 def test_c_call_alone():

@@ -120,6 +120,32 @@ def check_c_call():
     assert rc != 0 and 'n_bands' in msg
     rc, _, msg = raw_call(case['pix'], case['tod'], case['w'], x, lab, 2 ** 31 // npix + 1, L, npix, out_elems=8)
     assert rc != 0 and 'n_labels' in msg
+    check_degenerate_segments()
+
+
+def check_degenerate_segments():
+    """The segment counts at their smallest (L = 10, 7 pixels, one band, one label): only the
+    sentinel's segment -- through the label, then through the pixel -- exactly one live segment, and
+    a single offset."""
+    L, npix = 10, 7
+    rng = np.random.default_rng(11)
+    for what, NO, pix, label in (('all labelled -1', 3, None, -1), ('one pixel', 3, 4, 0), ('every pixel -2', 3, -2, 0),
+                                 ('one offset', 1, None, 0)):
+        n = NO * L
+        p = rng.integers(0, npix, n).astype(np.int32) if pix is None else np.full(n, pix, np.int32)
+        tod, w, x = rng.standard_normal(n), rng.uniform(0.5, 2.0, n), rng.standard_normal(NO)
+        lab = np.full(NO, label, np.int32)
+        want = oracle_split(p, tod, w, x, L, lab, 1, npix)
+        rc, got, msg = raw_call(p, tod, w, x, lab, 1, L, npix)
+        assert rc == 0, (what, msg)
+        for k in ('num', 'naive_num', 'weight', 'hits'):
+            assert np.array_equal(got[k][:, :, 0], want[k]), (what, k)
+        if label < 0 or pix == -2:
+            assert all(np.all(got[k] == 0.0) for k in got), what
+        elif pix == 4:
+            assert got['hits'][0, 4, 0] == n and np.count_nonzero(got['hits']) == 1, what
+        else:
+            assert got['hits'].sum() == n, what
 
 
 def test_c_call_alone():
