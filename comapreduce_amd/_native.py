@@ -117,6 +117,13 @@ _SIGS = {
     'comap_destripe_ground_dist_update': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                   c_void_p]),
     'comap_destripe_ground_dist_direction': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'comap_destripe_prior_create': (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int32, ctypes.POINTER(c_void_p)]),
+    'comap_destripe_prior_destroy': (c_int, [c_void_p]),
+    'comap_destripe_prior_tile': (c_int32, []),
+    'comap_destripe_prior_apply': (c_int, [c_void_p, c_void_p, c_void_p, c_int32]),
+    'comap_destripe_prior_apply_dot': (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p]),
+    'comap_destripe_prior_solve': (c_int, [c_void_p, c_double, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, P_int32]),
     'comap_destripe_split_maps': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
                                           c_int64, c_int32, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     'comap_destripe_split_div': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),

@@ -738,6 +738,37 @@ void ds_dot_part(comap_destriper *d, hipStream_t st, const double *a, const doub
 
 unsigned ds_upd_grid(int64_t NO) { return upd_grid(NO); }
 
+// ---- the native solve's own launches as the prior solve (destriper_prior.hip) enqueues them
+unsigned ds_launch_project_parts(const comap_destriper *d, hipStream_t st, const double *x, const double *num,
+                                 double *y, const int32_t *flags)
+{
+    return launch_project(d, st, x, num, nullptr, y, d->part, flags);
+}
+
+void ds_launch_update_fused(const comap_destriper *d, hipStream_t st, int npq, double *x, double *r, const double *p,
+                            const double *q, const int32_t *flags)
+{
+    k_cg_update_fused<1><<<upd_grid(d->NO), 256, 0, st>>>(d->scal, d->part, npq, x, r, p, q, d->NO, d->part + kPartMax,
+                                                          flags);
+}
+
+void ds_launch_direction_fused(const comap_destriper *d, hipStream_t st, double *p, const double *r, int32_t *flags)
+{
+    k_cg_direction_fused<1><<<grid_for(d->NO, kDirBlocks), 256, 0, st>>>(
+        d->scal, d->part + kPartMax, (int)upd_grid(d->NO), p, r, d->NO, flags, kPartMax, d->cf ? d->wbar : nullptr,
+        d->cf ? d->pt : nullptr);
+}
+
+void ds_scale(const comap_destriper *d, hipStream_t st, const double *x, double *xs)
+{
+    k_scale<1><<<grid_for(d->NO), 256, 0, st>>>(d->wbar, x, d->NO, xs, nullptr);
+}
+
+void ds_unpermute(const comap_destriper *d, hipStream_t st, const double *x, double *out)
+{
+    k_unpermute<1><<<grid_for(d->NO), 256, 0, st>>>(x, d->perm, d->NO, out);
+}
+
 void ds_div_map(hipStream_t st, const double *num, const double *h, int64_t n, double *out)
 {
     k_div_map<<<grid_for(n), 256, 0, st>>>(num, h, n, out);

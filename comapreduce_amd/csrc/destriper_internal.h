@@ -355,6 +355,21 @@ void ds_dot(comap_destriper *d, hipStream_t st, const double *a, const double *b
 void ds_dot_part(comap_destriper *d, hipStream_t st, const double *a, const double *b, int64_t n);
 unsigned ds_upd_grid(int64_t NO);
 void ds_div_map(hipStream_t st, const double *num, const double *h, int64_t n, double *out);
+// ... and the native solve's own four launches as the prior solve (destriper_prior.hip) enqueues them,
+// one band, on the problem's scalars, stop flags and partials (p.q at d->part, r.r at d->part + kPartMax):
+//   ds_launch_project_parts    the projection from the divided map, its p.q block partials in d->part;
+//                              returns its grid (= the partials written)
+//   ds_launch_update_fused     k_cg_update_fused over the first npq partials of d->part
+//   ds_launch_direction_fused  k_cg_direction_fused (count form: it also writes d->pt)
+//   ds_scale                   xs = wbar o x (the count form's bin input)
+//   ds_unpermute               out[perm[k]] = x[k]
+unsigned ds_launch_project_parts(const comap_destriper *d, hipStream_t st, const double *x, const double *num,
+                                 double *y, const int32_t *flags);
+void ds_launch_update_fused(const comap_destriper *d, hipStream_t st, int npq, double *x, double *r, const double *p,
+                            const double *q, const int32_t *flags);
+void ds_launch_direction_fused(const comap_destriper *d, hipStream_t st, double *p, const double *r, int32_t *flags);
+void ds_scale(const comap_destriper *d, hipStream_t st, const double *x, double *xs);
+void ds_unpermute(const comap_destriper *d, hipStream_t st, const double *x, double *out);
 
 inline int bits_for(uint64_t bound)   // bits that hold every key in [0, bound)
 {

@@ -73,6 +73,94 @@ def lane_tree_sum(v):
     return float(a[0])
 
 
+def _prior_runs(gid, n_groups):
+    """(s, e) int64 [n_groups]: the one run [s_g, e_g) of offsets every noise-prior group id
+    occupies (0, 0 for a group without offsets).  ValueError for an id outside [-1, n_groups) or
+    a group in more than one run."""
+    gid = np.asarray(gid).reshape(-1).astype(np.int64)
+    G = int(n_groups)
+    if gid.size and (gid.min() < -1 or gid.max() >= G):
+        raise ValueError(f'noise prior: group id out of range (valid: -1 .. {G - 1})')
+    first = np.nonzero(np.concatenate([[True], gid[1:] != gid[:-1]]) & (gid >= 0))[0] if gid.size else np.zeros(0, int)
+    last = np.nonzero(np.concatenate([gid[1:] != gid[:-1], [True]]) & (gid >= 0))[0] if gid.size else np.zeros(0, int)
+    if np.unique(gid[first]).size != first.size:
+        raise ValueError('noise prior: a group id occupies more than one run of offsets')
+    s, e = np.zeros(G, np.int64), np.zeros(G, np.int64)
+    s[gid[first]], e[gid[last]] = first, last + 1
+    return s, e
+
+
+def prior_apply_reference(v, gid, stencil):
+    """y = T v of the noise prior (comap_destripe_prior_apply) in NumPy, bit for bit: ``v`` f64 [n]
+    and ``gid`` [n] in the caller's offset order, ``stencil`` f64 [G, K + 1].  Group g occupies the
+    run [s_g, e_g); y_i = t_g[0] v_i, then for k = 1 .. K in this order y_i += t_g[k] v_{i-k} if
+    i - k >= s_g and y_i += t_g[k] v_{i+k} if i + k < e_g, every product and sum rounded to f64 on
+    its own; y_i = +0.0 where gid is -1.  ValueError for an id outside [-1, G) or a group in more
+    than one run."""
+    v = np.asarray(v, dtype=np.float64).reshape(-1)
+    gid = np.asarray(gid).reshape(-1).astype(np.int64)
+    t = np.asarray(stencil, dtype=np.float64)
+    if t.ndim != 2 or not 1 <= t.shape[1] - 1 <= 64:
+        raise ValueError('noise prior: stencil must be [n_groups, K + 1] with 1 <= K <= 64')
+    if gid.size != v.size:
+        raise ValueError('noise prior: one group id per offset')
+    s, e = _prior_runs(gid, t.shape[0])
+    has = gid >= 0
+    g = np.where(has, gid, 0)
+    si, ei, i = s[g], e[g], np.arange(v.size)
+    y = t[g, 0] * v
+    for k in range(1, t.shape[1]):
+        tk = t[g, k]
+        m = has & (i - k >= si)
+        y[m] = y[m] + tk[m] * v[i[m] - k]
+        m = has & (i + k < ei)
+        y[m] = y[m] + tk[m] * v[i[m] + k]
+    y[~has] = 0.0
+    return y
+
+
+def noise_prior_stencil(fknee, alpha, L, fs=50.0, taps=16, M=4096):
+    """The noise prior's stencil t[0 .. taps] for unit white variance: the inverse spectrum of the
+    L-sample means of correlated noise P_c(f) = (fknee / f)^(-alpha) (alpha < 0), sampled at fs.
+
+    For nu_j = j / M: P_a(nu) = (1/L) sum_{m<L} P_c(fs fold(phi_m)) D(phi_m), phi_m = (nu + m) / L,
+    fold(phi) = min(phi, 1 - phi), D(phi) = (sin(pi phi L) / (L sin(pi phi)))^2 with D(0) = 1 -- the
+    exact spectrum of the means, aliases included; P_c(0) = +inf, so 1 / P_a(0) = 0.
+    t[k] = (1 - k / (taps + 1)) (1/M) sum_j cos(2 pi j k / M) / P_a(nu_j): the triangular taper
+    convolves the symbol with a Fejer kernel, so it stays >= 0 and every finite section is positive
+    semi-definite, at the price of a weak zero-mean prior per group (a non-zero row sum)."""
+    K, L, M = int(taps), int(L), int(M)
+    if not 1 <= K <= 64:
+        raise ValueError(f'noise prior: taps must lie in 1 .. 64, not {taps}')
+    if not (np.isfinite(fknee) and fknee > 0 and np.isfinite(alpha) and alpha < 0):
+        raise ValueError(f'noise prior: needs fknee > 0 and alpha < 0, not {fknee}, {alpha}')
+    if L < 1 or M <= 2 * K:
+        raise ValueError('noise prior: needs L >= 1 and M > 2 taps')
+    phi = (np.arange(M)[:, None] / M + np.arange(L)[None, :]) / L
+    with np.errstate(divide='ignore', invalid='ignore'):
+        f = fs * np.minimum(phi, 1.0 - phi)
+        pc = np.where(f > 0, (fknee / np.where(f > 0, f, 1.0)) ** (-alpha), np.inf)
+        sn = np.sin(np.pi * phi)
+        D = np.where(sn != 0, (np.sin(np.pi * phi * L) / (L * np.where(sn != 0, sn, 1.0))) ** 2, 1.0)
+        pa = (pc * D).sum(axis=1) / L
+        inv = np.where(np.isfinite(pa) & (pa > 0), 1.0 / pa, 0.0)
+    k = np.arange(K + 1)
+    t = (np.cos(2 * np.pi * np.outer(k, np.arange(M)) / M) * inv[None, :]).sum(axis=1) / M
+    return (1.0 - k / (K + 1.0)) * t
+
+
+def fknee_from_red_noise(sigma_w, sigma_r, alpha):
+    """The knee frequency (Hz) of a ``red_noise_model`` fit sigma_w^2 + sigma_r^2 f^alpha:
+    (sigma_r / sigma_w)^(2 / |alpha|).  NaN (an invalid fit: the group gets no prior) unless
+    sigma_w > 0, sigma_r > 0, alpha < 0 and all three are finite.  Scalars or arrays."""
+    sw, sr, a = (np.asarray(v, dtype=np.float64) for v in (sigma_w, sigma_r, alpha))
+    sw, sr, a = np.broadcast_arrays(sw, sr, a)
+    ok = np.isfinite(sw) & np.isfinite(sr) & np.isfinite(a) & (sw > 0) & (sr > 0) & (a < 0)
+    out = np.full(ok.shape, np.nan)
+    out[ok] = (sr[ok] / sw[ok]) ** (2.0 / np.abs(a[ok]))
+    return out if out.ndim else float(out)
+
+
 class TimedAllreduce:
     """torch_allreduce with every call bracketed by HIP events on the current stream (the
     stream the CG kernels run on, which waits for the collective): the measured
@@ -952,6 +1040,152 @@ class GroundOps(_Vectors):
         return slope, c - slope * self.mu
 
 
+class PriorOps(_Vectors):
+    """The destriper operator with a noise prior on the offsets, A + T (MADAM's F^T W Z F +
+    C_a^-1), as the operator object ``cg_solve`` drives: comap_destripe_prior_* around a one-band
+    DeviceOps' own calls.  ``gid`` holds one int32 group id per offset in the CALLER's (time)
+    order, in [-1, G) with -1 = no prior, every group one contiguous run of offsets; ``stencil``
+    is float64 [G, K + 1], 1 <= K <= 64 (``prior_apply_reference`` states T).  The right-hand side
+    has no prior term.  Vectors are the DeviceOps' (internal offset order)."""
+
+    def __init__(self, ops, gid, stencil):
+        torch = ops.torch
+        if ops.nb != 1:
+            raise NotImplementedError('the noise prior solves one band (batched bands are not supported)')
+        self.ops, self.torch, self.dev, self.ctx, self.nb = ops, torch, ops.dev, ops.ctx, 1
+        self.n_offsets, self.npix = ops.n_offsets, ops.npix
+        st = _to_tensor(stencil, ops.dev, torch.float64).contiguous()
+        if st.dim() != 2 or not 1 <= st.shape[1] - 1 <= 64 or st.shape[0] < 1:
+            raise ValueError('noise prior: stencil must be [n_groups >= 1, K + 1] with 1 <= K <= 64')
+        gid = ops._t(gid, torch.int32)
+        if gid.numel() != self.n_offsets:
+            raise ValueError(f'noise prior: one group id per offset ({self.n_offsets}), not {gid.numel()}')
+        self.gid, self.stencil, self.G, self.K = gid, st, int(st.shape[0]), int(st.shape[1]) - 1
+        h = ctypes.c_void_p()
+        N.bind_stream(self.ctx, self.dev)
+        rc = N.lib().comap_destripe_prior_create(ops.h, N.dptr(gid), self.G, N.dptr(st), self.K, ctypes.byref(h))
+        if rc == -3:
+            raise ValueError(N.lib().comap_last_error(self.ctx).decode())
+        N.check(rc, self.ctx, 'comap_destripe_prior_create')
+        self.pr = h
+
+    def __del__(self):
+        try:
+            if getattr(self, 'pr', None) is not None:
+                self.torch.cuda.synchronize(self.dev)
+                N.lib().comap_destripe_prior_destroy(self.pr)
+                self.pr = None
+        except Exception:  # pragma: no cover
+            pass
+
+    def _c(self, fn, *args):
+        self.ops._c(fn, *args)
+
+    def natural(self, x):
+        return self.ops.natural(x)
+
+    def local_maps(self):
+        return self.ops.local_maps()
+
+    def prior_apply(self, v, out, accumulate=0):
+        """out = T v (accumulate: out += T v); v, out [N/L] in the internal offset order."""
+        self._c('comap_destripe_prior_apply', self.pr, self.ops._v(v), self.ops._v(out), int(accumulate))
+
+    # ---- operator pieces
+    def bin(self, x, mode, out):
+        self.ops.bin(x, mode, out)
+
+    def project(self, u, num, h, y, dot=None):
+        if u is None:                                 # b has no prior term
+            self.ops.project(None, num, h, y)
+            return
+        # u . (A u) by the base projection's own fused dot, then u . (T u) added to it: with a zero
+        # prior every bit of the plain solve stays in place (a dot of the finished vector through
+        # ops.dot would sum in another order)
+        self.ops.project(u, num, h, y, dot)
+        if dot is None:
+            self.prior_apply(u, y, accumulate=1)
+        else:
+            self._c('comap_destripe_prior_apply_dot', self.pr, self.ops._v(u), self.ops._v(y), 1, self.ops._s(dot))
+
+    def dot(self, a, b, out):
+        self.ops.dot(a, b, out)
+
+    def cg_update(self, rr, pq, x, r, p, q, rr_new):
+        self.ops.cg_update(rr, pq, x, r, p, q, rr_new)
+
+    def cg_direction(self, rr_new, rr, p, r):
+        self.ops.cg_direction(rr_new, rr, p, r)
+
+    # ---- single-rank native solve (no Python per iteration)
+    def solve_native(self, threshold, niter):
+        """comap_destripe_prior_solve: (x [N/L] in the CALLER's offset order, [iterations], maps
+        {k: [npix]}), as DeviceOps.solve_native returns them."""
+        ops = self.ops
+        x = ops.empty(self.n_offsets)                         # the solve writes x and every map in full
+        maps = {k: ops.empty(self.npix) for k in ('map', 'naive', 'weight', 'hits')}
+        it = ctypes.c_int32()
+        self._c('comap_destripe_prior_solve', self.pr, float(threshold), int(niter), N.dptr(x), N.dptr(maps['map']),
+                N.dptr(maps['naive']), N.dptr(maps['weight']), N.dptr(maps['hits']), ctypes.byref(it))
+        return x, [int(it.value)], maps
+
+
+def prior_tile():
+    """The caller-order offsets one workgroup of the prior kernel takes per sweep."""
+    return int(N.lib().comap_destripe_prior_tile())
+
+
+def _prior_check(prior, ground, multi):
+    """The combinations a noise prior does not support, raised before any device call."""
+    if prior is None:
+        return
+    if ground is not None and ground is not False:
+        raise NotImplementedError('the noise prior with the ground template is not supported')
+    if multi:
+        raise NotImplementedError('the noise prior solves one band: pass a 1-D tod (batched bands are not supported)')
+    if isinstance(prior, dict):
+        if prior.get('feedid') is None or prior.get('obsids') is None:
+            raise ValueError("a noise-prior model needs 'feedid' and 'obsids' per sample")
+        if 'table' not in prior and ('fknee' not in prior or 'alpha' not in prior):
+            raise ValueError("a noise-prior model needs 'fknee' and 'alpha', or a 'table' of them")
+    elif not (isinstance(prior, (tuple, list)) and len(prior) == 2):
+        raise ValueError('prior must be (gid, stencil) or a noise-model dict')
+
+
+def prior_from_model(ops, model, offset_length):
+    """(gid int32 [N/L], stencil tensor [G, taps + 1], keys) of a noise-model dict on DeviceOps
+    ``ops``: groups from ``ground_groups`` ((observation, feed), which must each be one run of
+    offsets), group g's stencil = its largest sample weight times ``noise_prior_stencil`` of its
+    (fknee, alpha): model['fknee'] / ['alpha'] for every group, or model['table'] {(obsid, feed):
+    (fknee, alpha)} per group.  A group without a valid model (absent, not finite, fknee <= 0 or
+    alpha >= 0) or without a non-zero weight (a flagged feed) gets no prior (id -1).  keys: the
+    (obsid, feed) pairs this rank holds."""
+    torch = ops.torch
+    taps = int(model.get('taps', 16))
+    gid, uobs, ufeed = ground_groups(model['feedid'], model['obsids'], offset_length)
+    G = uobs.size * ufeed.size
+    held = np.unique(gid)
+    keys = [(int(uobs[g // ufeed.size]), int(ufeed[g % ufeed.size])) for g in held]
+    table = model.get('table')
+    # w-bar_g: the group's largest sample weight, from the weights on the device
+    wbar = torch.zeros(max(G, 1), dtype=torch.float64, device=ops.dev)
+    wbar.scatter_reduce_(0, torch.from_numpy(gid).to(ops.dev).to(torch.int64), ops.w[0].reshape(-1, ops.L).amax(dim=1),
+                         reduce='amax', include_self=True)
+    weighted = wbar.cpu().numpy() > 0
+    t = np.zeros((max(G, 1), taps + 1))
+    cache, valid = {}, np.zeros(max(G, 1), bool)
+    for g, key in zip(held, keys):
+        fk, al = table.get(key, (np.nan, np.nan)) if table is not None else (model['fknee'], model['alpha'])
+        fk, al = float(fk), float(al)
+        if not (weighted[g] and np.isfinite(fk) and np.isfinite(al) and fk > 0 and al < 0):
+            continue
+        if (fk, al) not in cache:
+            cache[fk, al] = noise_prior_stencil(fk, al, offset_length, fs=float(model.get('fs', 50.0)), taps=taps)
+        t[g], valid[g] = cache[fk, al], True
+    gid = np.where(valid[gid], gid, -1).astype(np.int32)
+    return gid, torch.from_numpy(t).to(ops.dev) * wbar[:, None], keys
+
+
 _COPY_STREAMS = {}
 
 
@@ -1033,7 +1267,7 @@ class DeviceDestriper:
     counts are added across ranks, and every rank takes the same cut."""
 
     def __init__(self, pixels, tod, weights, offset_length, npix, device=None, keep=None, map_shape=None,
-                 ground=None, split=None, residuals=None, residual_groups=None, residual_cut=None):
+                 ground=None, split=None, residuals=None, residual_groups=None, residual_cut=None, prior=None):
         """map_shape (ny, nx): the map's row-major layout (CAR / WCS maps), when known; the
         operator then runs on a 2-D tiled internal pixel order (tiled_layout) and the maps
         come back in the caller's order.
@@ -1065,8 +1299,20 @@ class DeviceDestriper:
         not chi2 <= c (so a NaN is cut); if any is, the operator is rebuilt with the cut groups'
         weights zeroed and their offsets dropped (keep 0: they leave the hit map), solved ONCE
         more (not iterated) and the residuals recomputed; res['residuals'] gains 'cut' (bool) and
-        'chi2_first' (the first pass's chi2).  Not with ``ground`` either."""
+        'chi2_first' (the first pass's chi2).  Not with ``ground`` either.
+        prior: a noise prior on the offsets, (A + T) x = b (PriorOps; off by default) -- (gid,
+        stencil), one int32 group id per offset in [-1, G) (-1: no prior; every group one
+        contiguous run of offsets) and float64 [G, K + 1]; or a noise model {'fknee', 'alpha'[,
+        'taps': 16], 'feedid', 'obsids'} (or 'table': {(obsid, feed): (fknee, alpha)} in place of
+        the two values), whose groups are ``ground_groups``' and whose stencils are the group's
+        largest weight times ``noise_prior_stencil`` (``prior_from_model``).  One band, not with
+        ``ground``.  On one rank the solve is native (COMAP_DS_PRIOR_SOLVE=eager: ``cg_solve`` on
+        PriorOps); across ranks the problem is always sharded and every group must lie whole on
+        one rank (ValueError on every rank otherwise), so T is rank-local.  ``split`` and
+        ``residuals`` work with it: they only consume x."""
         self.layout, self.okey = None, None
+        self.prior, self.pops = None, None
+        _prior_check(prior, ground, np.ndim(tod) == 2 if not hasattr(tod, 'dim') else tod.dim() == 2)
         self.ground = None
         self.split = None
         self.resid, self.resid_cut, self.resid_axes = None, None, None
@@ -1101,11 +1347,12 @@ class DeviceDestriper:
         ranks = d is not None and d.get_world_size() > 1
         if ranks and os.environ.get('COMAP_DS_RANKS', 'shard') == 'gather':
             import warnings
-            for asked, what in ((ground, 'the ground template'), (split, 'split maps'), (residuals, 'residuals')):
+            for asked, what in ((ground, 'the ground template'), (split, 'split maps'), (residuals, 'residuals'),
+                                (prior, 'the noise prior')):
                 if asked is not None:
                     warnings.warn(f'COMAP_DS_RANKS=gather is not supported with {what}: sharding')
         if ranks:
-            if ground is None and split is None and residuals is None \
+            if ground is None and split is None and residuals is None and prior is None \
                     and self._choose_gather(d, pixels, tod, offset_length):
                 self._gather(d, pixels, tod, weights, keep, offset_length, npix, device)
                 return
@@ -1138,6 +1385,28 @@ class DeviceDestriper:
             _, tables = _on_every_rank('ground template set-up', set_up, (ValueError, IndexError), lambda t: t)
             if tables is not None:
                 merge_ground_tables(tables)     # two ranks holding one (observation, feed) fails on every rank
+        if prior is not None:
+            def set_up():
+                if isinstance(prior, dict):
+                    gid, stencil, keys = prior_from_model(self.ops, prior, int(offset_length))
+                else:
+                    gid, stencil = prior
+                    g = gid.cpu().numpy() if hasattr(gid, 'cpu') else np.asarray(gid)
+                    keys = [int(v) for v in np.unique(g[g >= 0])]
+                self.pops = N.retry_oom(PriorOps, self.ops, gid, stencil)
+                self.prior = (self.pops.gid, self.pops.stencil)
+                return keys
+
+            _, held = _on_every_rank('noise prior set-up', set_up, (ValueError, IndexError), lambda k: k)
+            if held is not None:
+                # (T is rank-local only when every group lies whole on one rank)
+                seen = {}
+                for rank, keys in enumerate(held):
+                    for k in keys:
+                        if k in seen:
+                            raise ValueError(f'noise prior: group {k} has offsets on ranks {seen[k]} and {rank}: '
+                                             'every group must lie on one rank')
+                        seen[k] = rank
 
     def _labels(self, labels, n_labels, what, times_npix=False):
         """(int32 CUDA labels [N/L], n_labels) of a split ('split') or of the residual groups;
@@ -1235,9 +1504,12 @@ class DeviceDestriper:
         keep = torch.ones((nbo, NO), dtype=torch.uint8, device=ops.dev) if ops.keep is None else ops.keep[:nbo].clone()
         keep[gone] = 0
         pix, tod, npix, dev = ops.pix, ops.tod[:nbo], ops.npix, ops.dev.index
+        self.pops = None                                                    # (the prior's handle borrows the problem)
         self.ops = None                                                     # (the old problem's buffers go first)
         del ops
         self.ops = N.retry_oom(DeviceOps, pix, tod, w, L, npix, dev, keep, self.okey)
+        if self.prior is not None:                                          # the same prior on the rebuilt operator
+            self.pops = N.retry_oom(PriorOps, self.ops, *self.prior)
 
     def solve(self, threshold=1e-6, niter=100, to_host=False, allreduce=None):
         """to_host: maps as host NumPy arrays (rank 0; None on the others) -- one
@@ -1437,7 +1709,8 @@ class DeviceDestriper:
             return self._solve_ground(threshold, niter, to_host)
         d = _dist()
         ops = self.ops
-        if to_host and self.gathered is None and (d is None or d.get_world_size() == 1) and self.resid is None:
+        if to_host and self.gathered is None and (d is None or d.get_world_size() == 1) and self.resid is None \
+                and self.prior is None:
             x, it, maps = ops.solve_native_host(threshold, niter, unmap=self.layout)
             maps['map2'] = maps['weight']
             if not self.multi:
@@ -1459,6 +1732,22 @@ class DeviceDestriper:
         if self.gathered is not None:
             x, it, maps, nb, nbands = self._solve_gathered(d, threshold, niter)
             split = lambda v: v.reshape(-1, nb).t()[:nbands].contiguous()   # noqa: E731
+        elif self.prior is not None:
+            # one rank: the native solve (COMAP_DS_PRIOR_SOLVE=eager: Python's cg_solve on PriorOps);
+            # across ranks cg_solve with the sharded all-reduces, T being rank-local
+            ranks = d is not None and d.get_world_size() > 1
+            mode = os.environ.get('COMAP_DS_PRIOR_SOLVE', 'native')
+            if mode not in ('native', 'eager'):
+                raise ValueError(f"COMAP_DS_PRIOR_SOLVE must be 'native' or 'eager', not {mode!r}")
+            if ranks or mode == 'eager':
+                x, it, h, nnum = cg_solve(self.pops, (allreduce or torch_allreduce) if ranks else (lambda t: t),
+                                          threshold, niter)
+                maps, m_internal = self._finish_maps(ops, x, h, nnum)
+                x, it = ops.natural(x), [it]
+            else:
+                x, it, maps = self.pops.solve_native(threshold, niter)
+                m_internal = maps['map']
+            split = ops.split_bands
         elif d is None or d.get_world_size() == 1:
             x, it, maps = ops.solve_native(threshold, niter)
             split = ops.split_bands
@@ -1578,7 +1867,7 @@ def maps_to_host(maps):
 def run_destriper(_pointing, _tod, _weights, offset_length, pixel_edges, az=None, el=None, ra=None, dec=None,
                   feedid=None, obsids=None, obsid_cuts=None, threshold=1e-6, niter=100, chi2_cutoff=100,
                   special_weight=None, healpix=False, device=None, map_shape=None, ground=False, split=None,
-                  residuals=False, residual_cut=None):
+                  residuals=False, residual_cut=None, prior=None):
     """Destriper.run_destriper (Destriper.py:456-503) on the GPU.
 
     ``pixel_edges[-1] + 1`` is the map size (bin_offset_map, :169).  Returns
@@ -1601,7 +1890,15 @@ def run_destriper(_pointing, _tod, _weights, offset_length, pixel_edges, az=None
     ignored, as in the reference): the residual chi-squared of tod - F x - P m per (observation,
     feed) and, with a cut, one more solve without the groups above c (DeviceDestriper); the
     result gains 'Residuals': {'obsids', 'feeds', 'chi2', 'count'[, 'cut', 'chi2_first']}, tables
-    [n_obs, n_feeds], on rank 0 and None on the other ranks.  Not together with ``ground``."""
+    [n_obs, n_feeds], on rank 0 and None on the other ranks.  Not together with ``ground``.
+    prior, an extension (off by default): a noise prior on the offsets, DeviceDestriper's ``prior``
+    -- (gid, stencil), or a noise model {'fknee', 'alpha'[, 'taps']} (or {'table': {(obsid, feed):
+    (fknee, alpha)}}) that takes its groups from ``feedid`` and ``obsids``.  One band; not together
+    with ``ground``."""
+    _prior_check(None if prior is None else (dict(prior, feedid=feedid, obsids=obsids) if isinstance(prior, dict)
+                                             else prior), ground, np.ndim(_tod) == 2)
+    if isinstance(prior, dict):
+        prior = dict(prior, feedid=feedid, obsids=obsids)
     if special_weight is not None:
         raise NotImplementedError('special_weight is unused by run_destriper in the reference (:482)')
     import torch
@@ -1617,7 +1914,8 @@ def run_destriper(_pointing, _tod, _weights, offset_length, pixel_edges, az=None
     dd = DeviceDestriper(np.asarray(_pointing), np.asarray(_tod, dtype=np.float64),
                          np.asarray(_weights, dtype=np.float64), int(offset_length), npix, device, map_shape=map_shape,
                          ground=(np.asarray(az, dtype=np.float64), feedid, obsids) if ground else None,
-                         split=None if specs is None else [(lab, len(names)) for lab, names in specs], **resid)
+                         split=None if specs is None else [(lab, len(names)) for lab, names in specs], prior=prior,
+                         **resid)
     res = dd.solve(threshold, niter, to_host=True)
     maps = res['maps']
     if maps is None:                     # a rank other than 0
@@ -1673,7 +1971,7 @@ def _split_entries(specs, splits, band=None):
 
 def run_destriper_bands(_pointing, _tods, _weights, offset_length, pixel_edges, keep=None, threshold=1e-6,
                         niter=100, device=None, map_shape=None, split=None, feedid=None, obsids=None,
-                        residuals=False, residual_cut=None):
+                        residuals=False, residual_cut=None, prior=None):
     """run_destriper for several sidebands on the same pointing in ONE batched
     device solve (the reference calls run_destriper once per band,
     run_destriper.py:146-189).  _tods/_weights [n_bands, N]; keep [n_bands, N/L]
@@ -1687,7 +1985,10 @@ def run_destriper_bands(_pointing, _tods, _weights, offset_length, pixel_edges, 
     per split; a band's 'hits' leave out the offsets it dropped.  With split, ranks other than 0
     get 'offsets' too (their own), as from run_destriper.
     residuals / residual_cut: as run_destriper's, every band's table from one device pass and the
-    cut decided per band; each band's dict gains 'Residuals' (None on ranks other than 0)."""
+    cut decided per band; each band's dict gains 'Residuals' (None on ranks other than 0).
+    prior: not supported (NotImplementedError): the noise prior solves one band."""
+    if prior is not None:
+        raise NotImplementedError('the noise prior solves one band: batched bands are not supported')
     import torch
     if device is None:
         device = torch.cuda.current_device()

@@ -21,7 +21,7 @@ import os
 import numpy as np
 
 from . import comapdata as COMAPData
-from .destriper import run_destriper, run_destriper_bands
+from .destriper import _on_every_rank, fknee_from_red_noise, run_destriper, run_destriper_bands
 from .fits import write_image_hdus
 from ..tools.parser import Parser, sex2deg
 
@@ -126,7 +126,7 @@ def main(filelistname, offset_length=50, feed_weights=None, prefix='fg9', output
          crval=['05:32:00.3', '+12:30:28.0'], crpix=[240, 240], ctype=['RA---CAR', 'DEC--CAR'],
          cdelt=[-0.016666, 0.016666], use_gain_filter=True, calibration=True, calibrator='TauA', threshold=1e-6,
          niter=100, healpix=False, bands=(0, 1, 2, 3), store=None, device=None, batch_bands=True, ground=False,
-         split=None, residuals=False, residual_cut=None):
+         split=None, residuals=False, residual_cut=None, noise_prior=None):
     """run_destriper.main (run_destriper.py:79-189).  ``store`` (tests) maps
     filename -> (datasets, attrs) instead of reading files; ``device`` is the
     rank's GPU (default: torch's current device, LOCAL_RANK under torchrun).
@@ -153,7 +153,17 @@ def main(filelistname, offset_length=50, feed_weights=None, prefix='fg9', output
     one more solve without the (observation, feed) groups whose chi-squared is not <= c
     (destriper.run_destriper); each band's entry gains 'Residuals' (None on ranks other than 0)
     and rank 0 writes <output_dir>/<prefix>_residuals_band<iband>.npz.  ``chi2_cutoff`` and
-    ``obsid_cuts`` stay ignored, as in the reference.  Not together with ``ground``."""
+    ``obsid_cuts`` stay ignored, as in the reference.  Not together with ``ground``.
+    ``noise_prior`` ([Inputs] noise_prior in the .ini; absent = off): a noise prior on the offsets
+    (destriper.run_destriper's ``prior``) -- (fknee, alpha[, taps]) applies one model to every
+    (observation, feed); 'fnoise' takes each file's ``fnoise_fits/fnoise_fit_parameters`` (the
+    Level-2 red-noise fits): per (file, feed, band) the medians of fknee and alpha over the scans
+    with a valid fit, no prior for a group without one, ValueError for a file without the dataset.
+    This takes the per-band loop, as ``ground`` does; the files written are the same.  Not together
+    with ``ground``."""
+    noise_prior = _prior_spec(noise_prior)
+    if noise_prior is not None and ground:
+        raise NotImplementedError('noise_prior with ground_template is not supported')
     if ground and (residuals or residual_cut is not None):
         raise NotImplementedError('residual_chi2 / residual_cut with ground_template is not supported')
     resid = bool(residuals) or residual_cut is not None
@@ -185,7 +195,11 @@ def main(filelistname, offset_length=50, feed_weights=None, prefix='fg9', output
         offset_length = 250
         threshold = 1
     out = {}
-    if batch_bands and len(bands) > 1 and not ground:
+    fnoise = None
+    if noise_prior == 'fnoise':
+        # (a rank's missing dataset fails every rank, before the solves' collectives)
+        fnoise, _ = _on_every_rank('noise prior', lambda: fnoise_tables(filelist, open_file, bands))
+    if batch_bands and len(bands) > 1 and not ground and noise_prior is None:
         r = COMAPData.read_comap_data_bands(filelist, map_info, bands=bands, offset_length=offset_length, feeds=feeds,
                                             use_gain_filter=use_gain_filter, calibration=calibration,
                                             calibrator=calibrator, healpix=healpix, store=store, device=device)
@@ -214,10 +228,15 @@ def main(filelistname, offset_length=50, feed_weights=None, prefix='fg9', output
             use_gain_filter=use_gain_filter, calibration=calibration, calibrator=calibrator, healpix=healpix,
             store=store, device=device)
         pixel_edges = _healpix_edges(pointing) if healpix else np.arange(nxpix * nypix)
+        prior = None
+        if fnoise is not None:
+            prior = {'table': fnoise[iband]}
+        elif noise_prior is not None:
+            prior = dict(zip(('fknee', 'alpha', 'taps'), noise_prior))
         maps = run_destriper(pointing, tod, weights, offset_length, pixel_edges, az, el, ra, dec, feedid, obsids,
                              obsid_cuts, threshold=threshold, niter=niter, chi2_cutoff=20,
                              device=device, map_shape=None if healpix else (nypix, nxpix), ground=ground,
-                             split=split or None, **rkw)
+                             split=split or None, prior=prior, **rkw)
         sky = {k: v for k, v in maps.items() if k not in ('Ground', 'offsets', 'Residuals')}    # (the writers iterate the dict: the maps only)
         if rank == 0:
             if healpix:
@@ -253,6 +272,69 @@ def residual_params(params):
     return bool(chi2), cut
 
 
+def _prior_spec(v):
+    """``main``'s noise_prior as None, 'fnoise' or (fknee, alpha, taps); ValueError otherwise."""
+    if v is None or v is False:
+        return None
+    if isinstance(v, str):
+        if v != 'fnoise':
+            raise ValueError(f"noise_prior must be 'fnoise' or <fknee>, <alpha>[, <taps>], not {v!r}")
+        return v
+    try:
+        vals = [float(x) for x in v]
+    except (TypeError, ValueError):
+        raise ValueError(f"noise_prior must be 'fnoise' or <fknee>, <alpha>[, <taps>], not {v!r}") from None
+    if len(vals) not in (2, 3):
+        raise ValueError(f'noise_prior takes <fknee>, <alpha>[, <taps>], not {len(vals)} values')
+    fknee, alpha, taps = vals[0], vals[1], vals[2] if len(vals) == 3 else 16.0
+    if not (np.isfinite(fknee) and fknee > 0):
+        raise ValueError(f'noise_prior: fknee must be a positive number, not {fknee}')
+    if not (np.isfinite(alpha) and alpha < 0):
+        raise ValueError(f'noise_prior: alpha must be a negative number, not {alpha}')
+    if taps != int(taps) or not 1 <= taps <= 64:
+        raise ValueError(f'noise_prior: taps must be a whole number in 1 .. 64, not {taps}')
+    return fknee, alpha, int(taps)
+
+
+def prior_params(params):
+    """``main``'s noise_prior from the [Inputs] section: ``noise_prior : fnoise`` or
+    ``noise_prior : <fknee>, <alpha>[, <taps>]``; an absent key, None or False means off.
+    ValueError for anything else."""
+    v = params.get('noise_prior')
+    if isinstance(v, bool) and v:
+        raise ValueError("[Inputs] noise_prior must be 'fnoise' or <fknee>, <alpha>[, <taps>]")
+    if isinstance(v, float):
+        raise ValueError('[Inputs] noise_prior takes <fknee>, <alpha>[, <taps>], not 1 value')
+    return _prior_spec(v)
+
+
+def fnoise_tables(filelist, open_file, bands):
+    """{band: {(obsid, feed): (fknee, alpha)}} from every file's Level-2 red-noise fits
+    ``fnoise_fits/fnoise_fit_parameters`` [feed row, band, scan, (sigma_white, sigma_red, alpha)]:
+    per (file, feed, band) the medians of fknee (``fknee_from_red_noise``) and alpha over the scans
+    with a valid fit; a (file, feed, band) without one is left out (its group gets no prior).
+    ValueError, naming it, for a file without the dataset."""
+    name = 'fnoise_fits/fnoise_fit_parameters'
+    out = {b: {} for b in bands}
+    for fn in filelist:
+        f = open_file(fn)
+        if name not in f:
+            raise ValueError(f'noise_prior fnoise: {fn} has no {name}')
+        par = np.asarray(f[name], dtype=np.float64)
+        feeds = np.asarray(f['spectrometer/feeds']).astype(np.int64)
+        obsid = int(os.path.basename(str(fn)).split('-')[1])
+        for row, feed in enumerate(feeds[:par.shape[0]]):
+            for b in bands:
+                if b >= par.shape[1]:
+                    continue
+                fits = par[row, b].reshape(-1, 3)
+                fknee = np.atleast_1d(fknee_from_red_noise(fits[:, 0], fits[:, 1], fits[:, 2]))
+                ok = np.isfinite(fknee)
+                if ok.any():
+                    out[b][obsid, int(feed)] = (float(np.median(fknee[ok])), float(np.median(fits[ok, 2])))
+    return out
+
+
 def cli(argv):
     """``__main__`` block of run_destriper.py (:191-212): everything from [Inputs]
     except use_gain_filter / calibration / calibrator from [ReadData]."""
@@ -272,4 +354,4 @@ def cli(argv):
                 niter=int(params['niter']), healpix=params['healpix'],
                 ground=bool(params.get('ground_template', False)),
                 split=[str(k) for k in as_list(split)] if split else None, residuals=residuals,
-                residual_cut=residual_cut)
+                residual_cut=residual_cut, noise_prior=prior_params(params))

@@ -455,6 +455,41 @@ int comap_destripe_ground_dist_update(comap_ground *g, double *scal_dev, double 
 int comap_destripe_ground_dist_direction(comap_ground *g, double *scal_dev, double *p_dev, const double *r_dev,
                                          int32_t *flags_dev);
 
+/* ------------------------------------------------------------ destriper noise prior */
+/* The offsets' prior covariance in the normal equations, (A + T) x = b (MADAM's F^T W Z F + C_a^-1;
+ * b has no prior term), on a one-band problem.  Offsets are taken in the CALLER's (time) order:
+ * gid_dev[o] in [-1, n_groups) is offset o's group (-1: no prior), every group one contiguous run
+ * [s_g, e_g) of offsets; stencil_dev f64 [n_groups][K + 1], 1 <= K <= 64.  T is block diagonal, group
+ * g's block the (e_g - s_g)-square finite section of the symmetric banded Toeplitz matrix with first
+ * row stencil[g].  y = T v in a fixed order, each product and sum rounded to f64 on its own:
+ *   y_i = t_g[0] v_i; for k = 1 .. K: if i - k >= s_g: y_i += t_g[k] v_{i-k};
+ *                                      if i + k <  e_g: y_i += t_g[k] v_{i+k};     y_i = +0.0 for gid -1.
+ * create copies gid and stencil, checks them on the device (one host wait) and returns -3 with
+ * comap_last_error text for an id out of range, a group in more than one run, or K out of bounds.
+ * The handle borrows d, which must outlive it. */
+typedef struct comap_prior comap_prior;
+int comap_destripe_prior_create(comap_destriper *d, const int32_t *gid_dev, int64_t n_groups,
+                                const double *stencil_dev, int32_t K, comap_prior **out);
+int comap_destripe_prior_destroy(comap_prior *pr);
+/* The caller-order offsets one workgroup of the apply kernel takes per sweep (tests place group ends
+ * on, before and behind its edges). */
+int32_t comap_destripe_prior_tile(void);
+/* out = T v (accumulate != 0: out += T v, one more rounded add per value); v and out f64 [N/L] in the
+ * problem's INTERNAL offset order (the kernel gathers through the permutation), v != out.  No
+ * atomics, no host synchronisation. */
+int comap_destripe_prior_apply(comap_prior *pr, const double *v_dev, double *out_dev, int32_t accumulate);
+/* The same, then dot_dev[0] += v . (T v) (block partials, then one fixed-order final): with
+ * comap_destripe_project's own p . (A p) already in dot_dev, the eager CG's p . q; a zero prior adds
+ * +0.0 and leaves every bit of the plain solve in place. */
+int comap_destripe_prior_apply_dot(comap_prior *pr, const double *v_dev, double *out_dev, int32_t accumulate,
+                                   double *dot_dev);
+/* comap_destripe_solve on (A + T): x = 0, CG to threshold / niter on the device (the plain solve's
+ * four launches per iteration plus the apply kernel, a device stop flag, replayed graph batches where
+ * the plain solve replays them), then x f64 [N/L] in the caller's order and the plain solve's maps
+ * [npix] (any may be NULL); iters_out[0] = the iterations run. */
+int comap_destripe_prior_solve(comap_prior *pr, double threshold, int32_t niter, double *x_dev, double *map_dev,
+                               double *naive_dev, double *weight_dev, double *hits_dev, int32_t *iters_out);
+
 /* ------------------------------------------------------------ split maps (Destriper.py:487-501) */
 /* Per-label maps of a solved problem, all labels in one pass: the reference's (commented)
  * "Create individual feed maps too" block for any labelling of the offsets.  label_dev[o] in
