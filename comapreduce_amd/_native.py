@@ -124,6 +124,9 @@ _SIGS = {
     'comap_destripe_prior_apply_dot': (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p]),
     'comap_destripe_prior_solve': (c_int, [c_void_p, c_double, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                            c_void_p, P_int32]),
+    'comap_destripe_mask_view': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_void_p)]),
+    'comap_destripe_solve_view': (c_int, [c_void_p, c_double, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, P_int32]),
     'comap_destripe_split_maps': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
                                           c_int64, c_int32, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     'comap_destripe_split_div': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),

@@ -778,13 +778,21 @@ extern "C" int comap_destripe_destroy(comap_destriper *d)
 {
     if (!d) return 0;
     COMAP_DEVICE_GUARD(d->ctx);
+    if (d->nviews > 0) return comap_fail(d->ctx, -1, "destroying a problem that still has a live solve-mask view");
     // every stream that may still read the buffers (the CG stream, the caller's) is idle
     // after a device sync; the blocks then go back to the caches
     (void)hipDeviceSynchronize();
-    void *b[] = {d->orow, d->opix, d->ow, d->ws, d->tw, d->prow, d->poff, d->pw, d->h, d->hits, d->nnum, d->part, d->scal,
-                 d->cg, d->flags, d->hrow, d->hprow, d->perm, d->ocnt, d->pcnt, d->wbar, d->pt, d->sbase, d->spix,
-                 d->sco};
-    comap_tmp_free_on(b, (int)(sizeof(b) / sizeof(b[0])), nullptr, true);
+    if (d->parent) {   // a solve-mask view: the index structure, wbar and hits are its parent's
+        void *b[] = {d->ow, d->ws, d->tw, d->pw, d->h, d->nnum, d->part, d->scal, d->cg, d->flags, d->ocnt, d->pcnt,
+                     d->pt, d->sco};
+        comap_tmp_free_on(b, (int)(sizeof(b) / sizeof(b[0])), nullptr, true);
+        --d->parent->nviews;
+    } else {
+        void *b[] = {d->orow, d->opix, d->ow, d->ws, d->tw, d->prow, d->poff, d->pw, d->h, d->hits, d->nnum, d->part,
+                     d->scal, d->cg, d->flags, d->hrow, d->hprow, d->perm, d->ocnt, d->pcnt, d->wbar, d->pt, d->sbase,
+                     d->spix, d->sco};
+        comap_tmp_free_on(b, (int)(sizeof(b) / sizeof(b[0])), nullptr, true);
+    }
     comap_pinned_free(d->flags_host);
     comap_pinned_free(d->thr_host);
     if (d->batch) (void)hipGraphExecDestroy(d->batch);
@@ -1040,8 +1048,10 @@ static int cg_setup(comap_destriper *d)
 // threshold / niter, then the final maps (:419-451).  Iterations are queued kCgBatch
 // at a time as one graph launch; the device-side stop flags make a band's iterations
 // after its convergence no-ops, so its iterates and count equal a per-iteration loop's.
-extern "C" int comap_destripe_solve(comap_destriper *d, double threshold, int32_t niter, double *x, double *map,
-                                    double *naive, double *weight, double *hits, int32_t *iters_out)
+// md: the problem the final maps are binned from -- d itself, or a solve-mask view's parent (the full
+// weights), on the same stream behind the CG with no host wait between.
+static int solve_on(comap_destriper *d, comap_destriper *md, double threshold, int32_t niter, double *x, double *map,
+                    double *naive, double *weight, double *hits, int32_t *iters_out)
 {
     if (!d || !x || niter < 0) return -1;
     COMAP_DEVICE_GUARD(d->ctx);
@@ -1114,13 +1124,29 @@ extern "C" int comap_destripe_solve(comap_destriper *d, double threshold, int32_
     COMAP_LAUNCH_CHECK(ctx);
     // final maps: map = (sum w tod - W x) / h ; naive = sum w tod / h
     if (map) {
-        launch_bin(d, st, cx, d->nnum, nullptr, num, nullptr);
-        k_div_map<<<grid_for(np), 256, 0, st>>>(num, d->h, np, map);
+        launch_bin(md, st, cx, md->nnum, nullptr, num, nullptr);
+        k_div_map<<<grid_for(np), 256, 0, st>>>(num, md->h, np, map);
     }
-    if (naive) k_div_map<<<grid_for(np), 256, 0, st>>>(d->nnum, d->h, np, naive);
+    if (naive) k_div_map<<<grid_for(np), 256, 0, st>>>(md->nnum, md->h, np, naive);
     COMAP_LAUNCH_CHECK(ctx);
-    if (weight) COMAP_CHECK(ctx, hipMemcpyAsync(weight, d->h, 8 * np, hipMemcpyDeviceToDevice, st));
-    if (hits) COMAP_CHECK(ctx, hipMemcpyAsync(hits, d->hits, 8 * np, hipMemcpyDeviceToDevice, st));
+    if (weight) COMAP_CHECK(ctx, hipMemcpyAsync(weight, md->h, 8 * np, hipMemcpyDeviceToDevice, st));
+    if (hits) COMAP_CHECK(ctx, hipMemcpyAsync(hits, md->hits, 8 * np, hipMemcpyDeviceToDevice, st));
     COMAP_CHECK(ctx, hipStreamSynchronize(st));
     return 0;
+}
+
+extern "C" int comap_destripe_solve(comap_destriper *d, double threshold, int32_t niter, double *x, double *map,
+                                    double *naive, double *weight, double *hits, int32_t *iters_out)
+{
+    return solve_on(d, d, threshold, niter, x, map, naive, weight, hits, iters_out);
+}
+
+// comap_destripe_solve's CG on a solve-mask view (the system of the masked weights), then the final
+// maps from the view's parent with the CG's own x: every sample binned with its full weight.
+extern "C" int comap_destripe_solve_view(comap_destriper *view, double threshold, int32_t niter, double *x, double *map,
+                                         double *naive, double *weight, double *hits, int32_t *iters_out)
+{
+    if (!view) return -1;
+    if (!view->parent) return comap_fail(view->ctx, -1, "comap_destripe_solve_view: not a solve-mask view");
+    return solve_on(view, view->parent, threshold, niter, x, map, naive, weight, hits, iters_out);
 }

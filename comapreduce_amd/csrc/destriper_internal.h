@@ -124,6 +124,10 @@ struct comap_destriper {
     hipStream_t cs = nullptr;      // CG stream (graph capture needs a non-default stream)
     hipEvent_t ev = nullptr;
     hipGraphExec_t batch = nullptr;   // kCgBatch iterations
+    // solve-mask view (destriper_mask.hip): a view borrows its parent's index structure, wbar and hits and
+    // owns its coefficients, ws / tw, h / nnum, pt and CG state; a parent counts its live views
+    comap_destriper *parent = nullptr;
+    int nviews = 0;
 };
 
 constexpr int kProjU = 4;         // entry loads in flight per k_ds_project lane

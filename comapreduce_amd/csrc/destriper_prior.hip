@@ -362,15 +362,17 @@ extern "C" int comap_destripe_prior_solve(comap_prior *pr, double threshold, int
     }
     if (iters_out) iters_out[0] = d->flags_host[3];
     ds_unpermute(d, st, x, x_out);
-    // final maps: map = (sum w tod - W x) / h ; naive = sum w tod / h
+    // final maps: map = (sum w tod - W x) / h ; naive = sum w tod / h -- of a solve-mask view's parent
+    // (the full weights) when the prior sits on a view, as comap_destripe_solve_view's
+    const comap_destriper *md = d->parent ? d->parent : d;
     if (map) {
-        ds_launch_bin(d, st, x, d->nnum, nullptr, num, nullptr, false, false);
-        ds_div_map(st, num, d->h, np, map);
+        ds_launch_bin(md, st, x, md->nnum, nullptr, num, nullptr, false, false);
+        ds_div_map(st, num, md->h, np, map);
     }
-    if (naive) ds_div_map(st, d->nnum, d->h, np, naive);
+    if (naive) ds_div_map(st, md->nnum, md->h, np, naive);
     COMAP_LAUNCH_CHECK(ctx);
-    if (weight) COMAP_CHECK(ctx, hipMemcpyAsync(weight, d->h, 8 * (size_t)np, hipMemcpyDeviceToDevice, st));
-    if (hits) COMAP_CHECK(ctx, hipMemcpyAsync(hits, d->hits, 8 * (size_t)np, hipMemcpyDeviceToDevice, st));
+    if (weight) COMAP_CHECK(ctx, hipMemcpyAsync(weight, md->h, 8 * (size_t)np, hipMemcpyDeviceToDevice, st));
+    if (hits) COMAP_CHECK(ctx, hipMemcpyAsync(hits, md->hits, 8 * (size_t)np, hipMemcpyDeviceToDevice, st));
     COMAP_CHECK(ctx, hipStreamSynchronize(st));
     return 0;
 }

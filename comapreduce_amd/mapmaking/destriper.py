@@ -446,6 +446,31 @@ class DeviceOps(_Vectors):
         N.check(rc, self.ctx, 'comap_destripe_create_bands')
         self.h = h
         self.n_offsets = int(N.lib().comap_destripe_n_offsets(h))
+        self.parent = None                          # (a solve-mask view's parent: masked_view)
+
+    def masked_view(self, mask_internal):
+        """The solve-mask view of this problem (comap_destripe_mask_view) as an ops object of its
+        own: the system of w' = w outside the masked pixels, 0 on them.  ``mask_internal``: uint8
+        CUDA [npix] in the problem's internal pixel order, non-zero = masked.  The view shares
+        ``pix``, ``tod`` and ``w`` and keeps this object alive; its native solves run the CG on
+        the view and bin the final maps from this problem (comap_destripe_solve_view)."""
+        torch = self.torch
+        if self.parent is not None:
+            raise ValueError('a solve-mask view of a view is not supported')
+        m = mask_internal
+        if not isinstance(m, torch.Tensor) or m.dtype != torch.uint8 or m.numel() != self.npix or not m.is_cuda:
+            raise ValueError(f'solve mask must be a uint8 device tensor with {self.npix} values (one per pixel)')
+        m = m.contiguous().reshape(-1)
+        v = object.__new__(DeviceOps)
+        v.__dict__.update({k: getattr(self, k) for k in ('torch', 'dev', 'ctx', 'pix', 'tod', 'w', 'keep', 'n_bands',
+                                                          'nb', 'L', 'npix', 'n_offsets')})
+        v.h, v.parent, v.mask = None, self, m
+        h = ctypes.c_void_p()
+        N.bind_stream(self.ctx, self.dev)
+        N.check(N.lib().comap_destripe_mask_view(self.h, N.dptr(self.pix), N.dptr(self.tod), N.dptr(self.w), N.dptr(m),
+                                                 ctypes.byref(h)), self.ctx, 'comap_destripe_mask_view')
+        v.h = h
+        return v
 
     def _t(self, a, dt):
         return _to_tensor(a, self.dev, dt).contiguous().reshape(-1)
@@ -656,7 +681,9 @@ class DeviceOps(_Vectors):
         x = self.empty(self.n_offsets * nb)                  # the solve writes x and every map in full
         maps = {k: self.empty(self.npix * nb) for k in ('map', 'naive', 'weight', 'hits')}
         it = (ctypes.c_int32 * nb)()
-        self._c('comap_destripe_solve', self.h, float(threshold), int(niter), N.dptr(x), N.dptr(maps['map']),
+        # (a solve-mask view: its CG, then the maps from its parent)
+        self._c('comap_destripe_solve' if self.parent is None else 'comap_destripe_solve_view', self.h,
+                float(threshold), int(niter), N.dptr(x), N.dptr(maps['map']),
                 N.dptr(maps['naive']), N.dptr(maps['weight']), N.dptr(maps['hits']),
                 ctypes.cast(it, ctypes.POINTER(ctypes.c_int32)))
         return x, [int(v) for v in it][:self.n_bands], maps
@@ -672,8 +699,9 @@ class DeviceOps(_Vectors):
         cur = torch.cuda.current_stream(self.dev)
         m = N.device_empty((4, npix * nb), torch.float64, self.dev)              # map, naive, weight, hits
         nn = self.empty(npix * nb)                                              # local_maps copies it in full
-        self._c('comap_destripe_local_maps', self.h, N.dptr(m[2]), N.dptr(m[3]), N.dptr(nn))
-        self._c('comap_destripe_div_map', self.h, N.dptr(nn), None, N.dptr(m[1]))
+        full = self.h if self.parent is None else self.parent.h                 # (a view's maps are its parent's)
+        self._c('comap_destripe_local_maps', full, N.dptr(m[2]), N.dptr(m[3]), N.dptr(nn))
+        self._c('comap_destripe_div_map', full, N.dptr(nn), None, N.dptr(m[1]))
         bands = m.view(4, npix, nb).permute(0, 2, 1)[:, :nbo]                    # [4, n_bands, npix] view
         # unmap: the caller's pixel order from the problem's internal (tiled) one
         static = bands[1:].contiguous() if unmap is None else bands[1:].index_select(2, unmap)
@@ -690,7 +718,8 @@ class DeviceOps(_Vectors):
         static.record_stream(cs)
         x = self.empty(self.n_offsets * nb)                                     # written in full by the solve
         it = (ctypes.c_int32 * nb)()
-        self._c('comap_destripe_solve', self.h, float(threshold), int(niter), N.dptr(x), N.dptr(m[0]), None, None,
+        self._c('comap_destripe_solve' if self.parent is None else 'comap_destripe_solve_view', self.h,
+                float(threshold), int(niter), N.dptr(x), N.dptr(m[0]), None, None,
                 None, ctypes.cast(it, ctypes.POINTER(ctypes.c_int32)))
         host[0].copy_(bands[0] if unmap is None else bands[0].index_select(1, unmap), non_blocking=True)
         cur.synchronize()
@@ -1152,6 +1181,80 @@ def _prior_check(prior, ground, multi):
         raise ValueError('prior must be (gid, stencil) or a noise-model dict')
 
 
+def _mask_check(solve_mask, ground, residual_cut, healpix=False):
+    """The combinations a solve mask does not support, raised before any device call."""
+    if solve_mask is None:
+        return
+    if ground is not None and ground is not False:
+        raise NotImplementedError('a solve mask with the ground template is not supported')
+    if residual_cut is not None:
+        raise NotImplementedError('a solve mask with residual_cut is not supported: the cut rebuilds the problem')
+    if healpix:
+        raise NotImplementedError('a solve mask on a HEALPix map is not supported')
+
+
+def solve_mask_flags(mask, npix, map_shape=None):
+    """The caller's solve mask as host uint8 [npix] (non-zero / True = masked): bool, integer or
+    float values, [npix] or, with ``map_shape`` (ny, nx), [ny, nx].  ValueError for another
+    length or dimension and for a non-finite value."""
+    m = mask.cpu().numpy() if hasattr(mask, 'cpu') else np.asarray(mask)
+    if m.dtype.kind not in 'biuf':
+        raise ValueError(f'solve mask must hold bool, integer or float flags, not {m.dtype}')
+    if m.dtype.kind == 'f' and not np.isfinite(m).all():
+        raise ValueError('solve mask holds a non-finite value')
+    if m.ndim == 2:
+        if map_shape is None or tuple(int(v) for v in map_shape) != m.shape:
+            raise ValueError(f'a 2-D solve mask needs map_shape = its shape {m.shape}, not {map_shape}')
+    elif m.ndim != 1:
+        raise ValueError(f'solve mask must be [npix] or [ny, nx], not {m.ndim}-dimensional')
+    if m.size != int(npix):
+        raise ValueError(f'solve mask must hold one flag per map pixel ({int(npix)}), not {m.size}')
+    return (m.reshape(-1) != 0).astype(np.uint8)
+
+
+def mask_from_map(m, weight, nsigma, grow=1):
+    """A solve mask from a first-pass map (host NumPy): pixel p of the 2-D map ``m`` is flagged when
+    weight_p > 0 and |m_p - median(m[weight > 0])| sqrt(weight_p) > nsigma; the flagged set is then
+    dilated ``grow`` times with the 3 x 3 cross (a pixel's four edge neighbours, no wrap at the map's
+    border).  Returns bool [ny, nx]."""
+    m, weight = np.asarray(m, dtype=np.float64), np.asarray(weight, dtype=np.float64)
+    if m.ndim != 2 or weight.shape != m.shape:
+        raise ValueError('mask_from_map takes a 2-D map and a weight map of the same shape')
+    nsigma, grow = float(nsigma), int(grow)
+    if not (np.isfinite(nsigma) and nsigma > 0) or grow < 0:
+        raise ValueError(f'mask_from_map: nsigma must be positive and grow >= 0, not {nsigma}, {grow}')
+    hit = weight > 0
+    out = np.zeros(m.shape, bool)
+    if not hit.any():
+        return out
+    med = np.median(m[hit])
+    with np.errstate(invalid='ignore'):
+        out[hit] = np.abs(m[hit] - med) * np.sqrt(weight[hit]) > nsigma
+    for _ in range(grow):
+        g = out.copy()
+        g[1:] |= out[:-1]
+        g[:-1] |= out[1:]
+        g[:, 1:] |= out[:, :-1]
+        g[:, :-1] |= out[:, 1:]
+        out = g
+    return out
+
+
+def _snr_spec(solve_mask):
+    """(nsigma, grow) when ``solve_mask`` is the two-pass form ('snr', nsigma[, grow]), else None."""
+    if isinstance(solve_mask, (tuple, list)) and len(solve_mask) in (2, 3) and isinstance(solve_mask[0], str):
+        if solve_mask[0] != 'snr':
+            raise ValueError(f"solve_mask: the two-pass form is ('snr', nsigma[, grow]), not {solve_mask!r}")
+        nsigma = float(solve_mask[1])
+        grow = solve_mask[2] if len(solve_mask) == 3 else 1
+        if not (np.isfinite(nsigma) and nsigma > 0):
+            raise ValueError(f'solve_mask snr: nsigma must be a positive number, not {solve_mask[1]!r}')
+        if float(grow) != int(grow) or int(grow) < 0:
+            raise ValueError(f'solve_mask snr: grow must be a whole number >= 0, not {grow!r}')
+        return nsigma, int(grow)
+    return None
+
+
 def prior_from_model(ops, model, offset_length):
     """(gid int32 [N/L], stencil tensor [G, taps + 1], keys) of a noise-model dict on DeviceOps
     ``ops``: groups from ``ground_groups`` ((observation, feed), which must each be one run of
@@ -1267,7 +1370,8 @@ class DeviceDestriper:
     counts are added across ranks, and every rank takes the same cut."""
 
     def __init__(self, pixels, tod, weights, offset_length, npix, device=None, keep=None, map_shape=None,
-                 ground=None, split=None, residuals=None, residual_groups=None, residual_cut=None, prior=None):
+                 ground=None, split=None, residuals=None, residual_groups=None, residual_cut=None, prior=None,
+                 solve_mask=None):
         """map_shape (ny, nx): the map's row-major layout (CAR / WCS maps), when known; the
         operator then runs on a 2-D tiled internal pixel order (tiled_layout) and the maps
         come back in the caller's order.
@@ -1309,10 +1413,25 @@ class DeviceDestriper:
         ``ground``.  On one rank the solve is native (COMAP_DS_PRIOR_SOLVE=eager: ``cg_solve`` on
         PriorOps); across ranks the problem is always sharded and every group must lie whole on
         one rank (ValueError on every rank otherwise), so T is rank-local.  ``split`` and
-        ``residuals`` work with it: they only consume x."""
+        ``residuals`` work with it: they only consume x.
+        solve_mask: a solve mask (MADAM's "inmask"; off by default) -- one flag per map pixel in the
+        caller's pixel order, bool / integer / float [npix] or, with ``map_shape``, [ny, nx];
+        non-zero = masked.  The offsets are fitted from the samples outside the masked pixels (w' =
+        0 on them; off-map samples keep their weight), on a view of the problem
+        (DeviceOps.masked_view: ``self.sops``); the maps, split maps and residuals then use every
+        sample with its full weight and those offsets (``self.ops``).  An offset wholly inside
+        the mask stays 0 -- or, with ``prior``, is carried across by its neighbours.  solve()
+        adds res['solve_mask'] = {'pixels', 'samples', 'empty_offsets'} (the masked pixels, and per
+        band the weighted samples masked and the offsets left without data, over all ranks).
+        Works with ``prior``, ``split``, ``residuals`` and batched bands; across ranks the problem
+        is always sharded.  Not with ``ground`` or ``residual_cut``.  ``set_solve_mask`` replaces
+        or removes the mask on the built problem."""
         self.layout, self.okey = None, None
         self.prior, self.pops = None, None
+        self.mask_info, self.map_shape, self.sops = None, map_shape, None
         _prior_check(prior, ground, np.ndim(tod) == 2 if not hasattr(tod, 'dim') else tod.dim() == 2)
+        _mask_check(solve_mask, ground, residual_cut)
+        self.npix_caller = int(npix)
         self.ground = None
         self.split = None
         self.resid, self.resid_cut, self.resid_axes = None, None, None
@@ -1348,17 +1467,20 @@ class DeviceDestriper:
         if ranks and os.environ.get('COMAP_DS_RANKS', 'shard') == 'gather':
             import warnings
             for asked, what in ((ground, 'the ground template'), (split, 'split maps'), (residuals, 'residuals'),
-                                (prior, 'the noise prior')):
+                                (prior, 'the noise prior'), (solve_mask, 'a solve mask')):
                 if asked is not None:
                     warnings.warn(f'COMAP_DS_RANKS=gather is not supported with {what}: sharding')
         if ranks:
-            if ground is None and split is None and residuals is None and prior is None \
+            if ground is None and split is None and residuals is None and prior is None and solve_mask is None \
                     and self._choose_gather(d, pixels, tod, offset_length):
                 self._gather(d, pixels, tod, weights, keep, offset_length, npix, device)
                 return
             if os.environ.get('COMAP_DS_COMPACT', '1') != '0':
                 pixels, npix = self._compact(pixels, int(npix), device)
         self.ops = N.retry_oom(DeviceOps, pixels, tod, weights, offset_length, npix, device, keep, self.okey)
+        self.sops = self.ops                        # the problem the CG solves (a view under a solve mask)
+        if solve_mask is not None:
+            self._mask_view(solve_mask)
         if residuals is not None:
             self.resid_cut = None if residual_cut is None else float(residual_cut)
             if residuals is True:
@@ -1393,7 +1515,7 @@ class DeviceDestriper:
                     gid, stencil = prior
                     g = gid.cpu().numpy() if hasattr(gid, 'cpu') else np.asarray(gid)
                     keys = [int(v) for v in np.unique(g[g >= 0])]
-                self.pops = N.retry_oom(PriorOps, self.ops, gid, stencil)
+                self.pops = N.retry_oom(PriorOps, self.sops, gid, stencil)
                 self.prior = (self.pops.gid, self.pops.stencil)
                 return keys
 
@@ -1407,6 +1529,53 @@ class DeviceDestriper:
                             raise ValueError(f'noise prior: group {k} has offsets on ranks {seen[k]} and {rank}: '
                                              'every group must lie on one rank')
                         seen[k] = rank
+
+    def _mask_view(self, solve_mask):
+        """self.sops = the view of self.ops under ``solve_mask`` (the caller's pixel order), and
+        self.mask_info; a rank's bad mask fails on every rank."""
+        ops = self.ops
+        torch = ops.torch
+
+        def set_up():
+            flags = solve_mask_flags(solve_mask, self.npix_caller, self.map_shape)
+            m = torch.from_numpy(flags).to(ops.dev)
+            if self.layout is not None:             # onto the tiled layout (padding pixels unmasked)
+                t = torch.zeros(self.npix_full, dtype=torch.uint8, device=ops.dev)
+                t[self.layout.to(torch.int64)] = m
+                m = t
+            if self.hit_index is not None:          # a mask pixel the compaction dropped is simply unused
+                m = m[self.hit_index]
+            return m.contiguous(), flags
+
+        (m, flags), _ = _on_every_rank('solve mask', set_up)
+        self.sops = N.retry_oom(ops.masked_view, m)
+        # what the mask took, per band: weighted samples on masked pixels, offsets left without any
+        on = (ops.pix >= 0) & (m[ops.pix.clamp(min=0).to(torch.int64)] != 0)
+        had = (ops.w != 0)
+        gone = had & on[None, :]
+        left = (had & ~on[None, :]).reshape(ops.nb, ops.n_offsets, ops.L).any(dim=2)
+        empty = had.reshape(ops.nb, ops.n_offsets, ops.L).any(dim=2) & ~left
+        counts = torch.stack([gone.sum(dim=1), empty.sum(dim=1)]).to(torch.int64)
+        torch_allreduce(counts)
+        counts = counts[:, :ops.n_bands].cpu().numpy()
+        one = (lambda v: int(v[0])) if not self.multi else (lambda v: v.copy())
+        self.mask_info = {'pixels': int(flags.sum()), 'samples': one(counts[0]), 'empty_offsets': one(counts[1])}
+        self.mask_flags = flags
+
+    def set_solve_mask(self, solve_mask):
+        """Replace the solve mask (None: remove it) on the built problem: only the view is rebuilt
+        -- the parent problem, the split and residual labels and the prior's stencils stay; with
+        a prior its handle is re-created on the new view."""
+        _mask_check(solve_mask, self.ground, self.resid_cut)
+        if self.gathered is not None:
+            raise NotImplementedError('a solve mask on a gathered problem is not supported: build with solve_mask')
+        self.pops = None                            # (the prior's handle borrows the view)
+        self.sops = self.ops
+        self.mask_info = None
+        if solve_mask is not None:
+            self._mask_view(solve_mask)
+        if self.prior is not None:
+            self.pops = N.retry_oom(PriorOps, self.sops, *self.prior)
 
     def _labels(self, labels, n_labels, what, times_npix=False):
         """(int32 CUDA labels [N/L], n_labels) of a split ('split') or of the residual groups;
@@ -1508,6 +1677,7 @@ class DeviceDestriper:
         self.ops = None                                                     # (the old problem's buffers go first)
         del ops
         self.ops = N.retry_oom(DeviceOps, pix, tod, w, L, npix, dev, keep, self.okey)
+        self.sops = self.ops                                                # (no solve mask with a cut: _mask_check)
         if self.prior is not None:                                          # the same prior on the rebuilt operator
             self.pops = N.retry_oom(PriorOps, self.ops, *self.prior)
 
@@ -1708,10 +1878,11 @@ class DeviceDestriper:
         if self.ground is not None:
             return self._solve_ground(threshold, niter, to_host)
         d = _dist()
-        ops = self.ops
+        ops = self.ops                              # the full problem ...
+        sops = ops if self.sops is None else self.sops      # ... and the one the CG solves (its view under a mask)
         if to_host and self.gathered is None and (d is None or d.get_world_size() == 1) and self.resid is None \
                 and self.prior is None:
-            x, it, maps = ops.solve_native_host(threshold, niter, unmap=self.layout)
+            x, it, maps = sops.solve_native_host(threshold, niter, unmap=self.layout)
             maps['map2'] = maps['weight']
             if not self.multi:
                 res = {'x': x, 'iters': it[0], 'maps': {k: v[0] for k, v in maps.items()}}
@@ -1719,6 +1890,8 @@ class DeviceDestriper:
                 res = {'x': ops.split_bands(x), 'iters': it, 'maps': maps}
             if self.split is not None:           # after the overlapped solve, on the device x
                 res['splits'] = self._splits_to_host(self._split_maps(x))
+            if self.mask_info is not None:
+                res['solve_mask'] = dict(self.mask_info)
             return res
         if to_host:
             res = self._solve(threshold, niter, False, None)
@@ -1749,7 +1922,7 @@ class DeviceDestriper:
                 m_internal = maps['map']
             split = ops.split_bands
         elif d is None or d.get_world_size() == 1:
-            x, it, maps = ops.solve_native(threshold, niter)
+            x, it, maps = sops.solve_native(threshold, niter)
             split = ops.split_bands
             m_internal = maps['map']
         else:
@@ -1766,7 +1939,7 @@ class DeviceDestriper:
                     import warnings
                     warnings.warn(f'COMAP_DS_GRAPH=1 needs the nccl (RCCL) backend, not {d.get_backend()}: '
                                   'using the eager CG driver')
-            x, it, h, nnum = solver(ops, allreduce or torch_allreduce, threshold, niter)
+            x, it, h, nnum = solver(sops, allreduce or torch_allreduce, threshold, niter)
             maps, m_internal = self._finish_maps(ops, x, h, nnum)
             it = it[:ops.n_bands]
             x = ops.natural(x)
@@ -1777,6 +1950,8 @@ class DeviceDestriper:
         extra = {} if self.split is None else {'splits': self._split_maps(x)}
         if self.resid is not None:
             extra['residuals'] = self._residuals(x, m_internal)
+        if self.mask_info is not None:
+            extra['solve_mask'] = dict(self.mask_info)
         if not self.multi:
             maps['map2'] = maps['weight']
             return {'x': x, 'iters': it[0], 'maps': maps, **extra}
@@ -1792,8 +1967,10 @@ class DeviceDestriper:
         the problem's internal (compacted) pixels, which the residual pass reads."""
         ops = self.ops
         n = ops.npix * ops.nb
-        _, hits, _ = ops.local_maps()
+        h0, hits, n0 = ops.local_maps()
         torch_allreduce(hits)
+        if self.sops is not ops:                    # a solve mask: the CG's h and nnum are the view's
+            h, nnum = torch_allreduce(h0), torch_allreduce(n0)
         num = ops.zeros(n)
         op.bin(u, 1, num)
         torch_allreduce(num)
@@ -1867,7 +2044,7 @@ def maps_to_host(maps):
 def run_destriper(_pointing, _tod, _weights, offset_length, pixel_edges, az=None, el=None, ra=None, dec=None,
                   feedid=None, obsids=None, obsid_cuts=None, threshold=1e-6, niter=100, chi2_cutoff=100,
                   special_weight=None, healpix=False, device=None, map_shape=None, ground=False, split=None,
-                  residuals=False, residual_cut=None, prior=None):
+                  residuals=False, residual_cut=None, prior=None, solve_mask=None):
     """Destriper.run_destriper (Destriper.py:456-503) on the GPU.
 
     ``pixel_edges[-1] + 1`` is the map size (bin_offset_map, :169).  Returns
@@ -1894,7 +2071,18 @@ def run_destriper(_pointing, _tod, _weights, offset_length, pixel_edges, az=None
     prior, an extension (off by default): a noise prior on the offsets, DeviceDestriper's ``prior``
     -- (gid, stencil), or a noise model {'fknee', 'alpha'[, 'taps']} (or {'table': {(obsid, feed):
     (fknee, alpha)}}) that takes its groups from ``feedid`` and ``obsids``.  One band; not together
-    with ``ground``."""
+    with ``ground``.
+    solve_mask, an extension (off by default): DeviceDestriper's ``solve_mask`` -- one flag per map
+    pixel ([npix], or [ny, nx] with ``map_shape``); the offsets are fitted outside the masked pixels,
+    the maps binned from every sample.  The result gains 'solve_mask': {'pixels', 'samples',
+    'empty_offsets', 'mask'} ('mask': the flags, host uint8 [npix]).  ('snr', nsigma[, grow]) is the
+    two-pass form, which needs ``map_shape``: a plain solve, ``mask_from_map`` of its map and weight map
+    (rank 0's, handed to every rank), ``set_solve_mask`` on the same set-up and the solve again.  Not
+    with ``ground``, ``residual_cut`` or ``healpix``."""
+    _mask_check(solve_mask, ground, residual_cut, healpix)
+    snr = _snr_spec(solve_mask)
+    if snr is not None and map_shape is None:
+        raise ValueError("solve_mask ('snr', ...) needs map_shape: the mask is grown on the 2-D map")
     _prior_check(None if prior is None else (dict(prior, feedid=feedid, obsids=obsids) if isinstance(prior, dict)
                                              else prior), ground, np.ndim(_tod) == 2)
     if isinstance(prior, dict):
@@ -1915,12 +2103,24 @@ def run_destriper(_pointing, _tod, _weights, offset_length, pixel_edges, az=None
                          np.asarray(_weights, dtype=np.float64), int(offset_length), npix, device, map_shape=map_shape,
                          ground=(np.asarray(az, dtype=np.float64), feedid, obsids) if ground else None,
                          split=None if specs is None else [(lab, len(names)) for lab, names in specs], prior=prior,
-                         **resid)
+                         solve_mask=None if snr is not None else solve_mask, **resid)
     res = dd.solve(threshold, niter, to_host=True)
+    if snr is not None:
+        first = res['maps']
+        ny, nx = (int(v) for v in map_shape)
+        found = [None if first is None else mask_from_map(np.reshape(first['map'], (ny, nx)),
+                                                          np.reshape(first['weight'], (ny, nx)), *snr)]
+        d = _dist()
+        if d is not None and d.get_world_size() > 1:
+            d.broadcast_object_list(found, src=0)
+        dd.set_solve_mask(found[0])
+        res = dd.solve(threshold, niter, to_host=True)
     maps = res['maps']
     if maps is None:                     # a rank other than 0
         maps = {'map': None, 'naive': None, 'weight': None, 'map2': None}
     out = {'All': maps, 'Ground': res['ground']} if ground else {'All': maps}
+    if solve_mask is not None:
+        out['solve_mask'] = dict(res['solve_mask'], mask=dd.mask_flags)
     if resid:
         out['Residuals'] = _residual_table(dd, res['residuals'])
     if specs is not None:
@@ -1971,7 +2171,7 @@ def _split_entries(specs, splits, band=None):
 
 def run_destriper_bands(_pointing, _tods, _weights, offset_length, pixel_edges, keep=None, threshold=1e-6,
                         niter=100, device=None, map_shape=None, split=None, feedid=None, obsids=None,
-                        residuals=False, residual_cut=None, prior=None):
+                        residuals=False, residual_cut=None, prior=None, solve_mask=None):
     """run_destriper for several sidebands on the same pointing in ONE batched
     device solve (the reference calls run_destriper once per band,
     run_destriper.py:146-189).  _tods/_weights [n_bands, N]; keep [n_bands, N/L]
@@ -1986,7 +2186,12 @@ def run_destriper_bands(_pointing, _tods, _weights, offset_length, pixel_edges, 
     get 'offsets' too (their own), as from run_destriper.
     residuals / residual_cut: as run_destriper's, every band's table from one device pass and the
     cut decided per band; each band's dict gains 'Residuals' (None on ranks other than 0).
-    prior: not supported (NotImplementedError): the noise prior solves one band."""
+    prior: not supported (NotImplementedError): the noise prior solves one band.
+    solve_mask: as run_destriper's, one mask for all bands (the two-pass 'snr' form is per band:
+    NotImplementedError here); each band's dict gains 'solve_mask' with that band's counts."""
+    _mask_check(solve_mask, None, residual_cut)
+    if _snr_spec(solve_mask) is not None:
+        raise NotImplementedError("solve_mask ('snr', ...) is built per band: call run_destriper per band")
     if prior is not None:
         raise NotImplementedError('the noise prior solves one band: batched bands are not supported')
     import torch
@@ -2000,7 +2205,8 @@ def run_destriper_bands(_pointing, _tods, _weights, offset_length, pixel_edges, 
     specs = split_specs(split, feedid, obsids, offset_length)
     dd = DeviceDestriper(np.asarray(_pointing), tods, np.asarray(_weights, dtype=np.float64), int(offset_length), npix,
                          device, keep=None if keep is None else np.asarray(keep, dtype=np.uint8), map_shape=map_shape,
-                         split=None if specs is None else [(lab, len(names)) for lab, names in specs], **resid)
+                         split=None if specs is None else [(lab, len(names)) for lab, names in specs],
+                         solve_mask=solve_mask, **resid)
     res = dd.solve(threshold, niter, to_host=True)
     d = _dist()
     rank = d.get_rank() if d is not None else 0
@@ -2008,6 +2214,10 @@ def run_destriper_bands(_pointing, _tods, _weights, offset_length, pixel_edges, 
     hm = res['maps']
     for b in range(tods.shape[0]):
         extra = {} if specs is None else _split_entries(specs, res['splits'], band=b)
+        if solve_mask is not None:
+            sm = res['solve_mask']
+            extra['solve_mask'] = {'pixels': sm['pixels'], 'samples': int(sm['samples'][b]),
+                                   'empty_offsets': int(sm['empty_offsets'][b]), 'mask': dd.mask_flags}
         if resid:
             extra['Residuals'] = _residual_table(dd, res['residuals'], band=b)
         if rank != 0:

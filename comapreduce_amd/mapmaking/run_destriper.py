@@ -21,8 +21,9 @@ import os
 import numpy as np
 
 from . import comapdata as COMAPData
-from .destriper import _on_every_rank, fknee_from_red_noise, run_destriper, run_destriper_bands
-from .fits import write_image_hdus
+from .destriper import (_mask_check, _on_every_rank, _snr_spec, fknee_from_red_noise, run_destriper,
+                        run_destriper_bands)
+from .fits import read_image_hdus, write_image_hdus
 from ..tools.parser import Parser, sex2deg
 
 CALIBRATORS = COMAPData.CALIBRATORS
@@ -35,8 +36,9 @@ def _rank_size():
     return 0, 1
 
 
-def write_map(prefix, maps, map_info, output_dir, iband, postfix=''):
-    """run_destriper.write_map (run_destriper.py:19-50)."""
+def write_map(prefix, maps, map_info, output_dir, iband, postfix='', solve_mask=None):
+    """run_destriper.write_map (run_destriper.py:19-50).  solve_mask (flags, one per pixel): one more
+    image HDU 'SolveMask' (0 / 1) behind the others; without it the files are the reference's."""
     os.makedirs(output_dir, exist_ok=True)
     wcs, nx, ny = map_info['wcs'], map_info['nxpix'], map_info['nypix']
     cards = wcs.to_header()
@@ -49,6 +51,8 @@ def write_map(prefix, maps, map_info, output_dir, iband, postfix=''):
                 images.append(('Noise', np.reshape(np.sqrt(1. / v['weight']), (ny, nx))))
         if 'hits' in v:
             images.append(('Hits', np.reshape(v['hits'], (ny, nx))))
+        if solve_mask is not None:
+            images.append(('SolveMask', np.reshape(np.asarray(solve_mask) != 0, (ny, nx)).astype(np.float64)))
         fname = '{}/{}_{}_Band{:02d}.fits'.format(output_dir, k, prefix, iband)
         write_image_hdus(fname, images, cards)
 
@@ -126,7 +130,7 @@ def main(filelistname, offset_length=50, feed_weights=None, prefix='fg9', output
          crval=['05:32:00.3', '+12:30:28.0'], crpix=[240, 240], ctype=['RA---CAR', 'DEC--CAR'],
          cdelt=[-0.016666, 0.016666], use_gain_filter=True, calibration=True, calibrator='TauA', threshold=1e-6,
          niter=100, healpix=False, bands=(0, 1, 2, 3), store=None, device=None, batch_bands=True, ground=False,
-         split=None, residuals=False, residual_cut=None, noise_prior=None):
+         split=None, residuals=False, residual_cut=None, noise_prior=None, solve_mask=None):
     """run_destriper.main (run_destriper.py:79-189).  ``store`` (tests) maps
     filename -> (datasets, attrs) instead of reading files; ``device`` is the
     rank's GPU (default: torch's current device, LOCAL_RANK under torchrun).
@@ -160,7 +164,16 @@ def main(filelistname, offset_length=50, feed_weights=None, prefix='fg9', output
     Level-2 red-noise fits): per (file, feed, band) the medians of fknee and alpha over the scans
     with a valid fit, no prior for a group without one, ValueError for a file without the dataset.
     This takes the per-band loop, as ``ground`` does; the files written are the same.  Not together
-    with ``ground``."""
+    with ``ground``.
+    ``solve_mask`` ([Inputs] solve_mask in the .ini; absent = off): fit the offsets from the samples
+    outside a pixel mask and bin the maps from every sample (destriper.run_destriper's
+    ``solve_mask``).  A path names a FITS file whose first image HDU, (nypix, nxpix), is the mask
+    (non-zero = masked; NaN is a ValueError); ('snr', nsigma[, grow]) is the two-pass form, per band:
+    a plain solve, ``mask_from_map`` of its map, and the solve again on the same set-up, which takes
+    the per-band loop as ``noise_prior`` does.  Every file written gains a 'SolveMask' image HDU; each
+    band's entry gains 'solve_mask'.  Not with ``ground``, ``residual_cut`` or ``healpix``."""
+    solve_mask = _mask_spec(solve_mask)
+    _mask_check(solve_mask, ground or None, residual_cut, healpix)
     noise_prior = _prior_spec(noise_prior)
     if noise_prior is not None and ground:
         raise NotImplementedError('noise_prior with ground_template is not supported')
@@ -195,11 +208,14 @@ def main(filelistname, offset_length=50, feed_weights=None, prefix='fg9', output
         offset_length = 250
         threshold = 1
     out = {}
+    mkw = {}
+    if solve_mask is not None:
+        mkw = {'solve_mask': solve_mask if _snr_spec(solve_mask) else read_solve_mask(solve_mask, nypix, nxpix)}
     fnoise = None
     if noise_prior == 'fnoise':
         # (a rank's missing dataset fails every rank, before the solves' collectives)
         fnoise, _ = _on_every_rank('noise prior', lambda: fnoise_tables(filelist, open_file, bands))
-    if batch_bands and len(bands) > 1 and not ground and noise_prior is None:
+    if batch_bands and len(bands) > 1 and not ground and noise_prior is None and not _snr_spec(solve_mask):
         r = COMAPData.read_comap_data_bands(filelist, map_info, bands=bands, offset_length=offset_length, feeds=feeds,
                                             use_gain_filter=use_gain_filter, calibration=calibration,
                                             calibrator=calibrator, healpix=healpix, store=store, device=device)
@@ -207,18 +223,23 @@ def main(filelistname, offset_length=50, feed_weights=None, prefix='fg9', output
         res = run_destriper_bands(r['pointing'], r['tod'], r['weights'], offset_length, pixel_edges, keep=r['keep'],
                                   threshold=threshold, niter=niter, device=device,
                                   map_shape=None if healpix else (nypix, nxpix), split=split or None,
-                                  feedid=r['feedid'], obsids=r['obsids'], **rkw)
+                                  feedid=r['feedid'], obsids=r['obsids'], **rkw, **mkw)
         for iband, maps in zip(bands, res):
-            sky = {k: v for k, v in maps.items() if k not in ('iters', 'offsets', 'Residuals')}    # 'All' and the split maps
+            sky = {k: v for k, v in maps.items()
+                   if k not in ('iters', 'offsets', 'Residuals', 'solve_mask')}    # 'All' and the split maps
             if rank == 0:
                 if healpix:
                     write_map_healpix(prefix, sky, r['remapping_array'], map_info, output_dir, iband)
+                elif mkw:
+                    write_map(prefix, sky, map_info, output_dir, iband, solve_mask=maps['solve_mask']['mask'])
                 else:
                     write_map(prefix, sky, map_info, output_dir, iband)
                 if resid:
                     _write_residuals(output_dir, prefix, iband, maps['Residuals'])
             if resid:
                 sky = dict(sky, Residuals=maps['Residuals'])
+            if mkw:
+                sky = dict(sky, solve_mask=maps['solve_mask'])
             # (with split maps the band's entry keeps the offsets they were binned with)
             out[iband] = dict(sky, offsets=maps['offsets']) if split else sky       # (on every rank, as per band)
         return out
@@ -236,11 +257,14 @@ def main(filelistname, offset_length=50, feed_weights=None, prefix='fg9', output
         maps = run_destriper(pointing, tod, weights, offset_length, pixel_edges, az, el, ra, dec, feedid, obsids,
                              obsid_cuts, threshold=threshold, niter=niter, chi2_cutoff=20,
                              device=device, map_shape=None if healpix else (nypix, nxpix), ground=ground,
-                             split=split or None, prior=prior, **rkw)
-        sky = {k: v for k, v in maps.items() if k not in ('Ground', 'offsets', 'Residuals')}    # (the writers iterate the dict: the maps only)
+                             split=split or None, prior=prior, **rkw, **mkw)
+        sky = {k: v for k, v in maps.items()
+               if k not in ('Ground', 'offsets', 'Residuals', 'solve_mask')}    # (the writers iterate the dict: the maps only)
         if rank == 0:
             if healpix:
                 write_map_healpix(prefix, sky, remap, map_info, output_dir, iband)
+            elif mkw:
+                write_map(prefix, sky, map_info, output_dir, iband, solve_mask=maps['solve_mask']['mask'])
             else:
                 write_map(prefix, sky, map_info, output_dir, iband)
             if ground:
@@ -270,6 +294,43 @@ def residual_params(params):
     if not (chi2 is None or isinstance(chi2, bool)):
         raise ValueError(f'[Inputs] residual_chi2 must be True or False, not {chi2!r}')
     return bool(chi2), cut
+
+
+def read_solve_mask(fname, nypix, nxpix):
+    """The solve mask of a FITS file: its first image HDU, (nypix, nxpix), non-zero = masked, as bool
+    [nypix, nxpix].  ValueError for another shape and for a NaN."""
+    hdus = read_image_hdus(fname)
+    if not hdus:
+        raise ValueError(f'solve_mask: {fname} holds no image HDU')
+    img = hdus[0][1]
+    if img.shape != (int(nypix), int(nxpix)):
+        raise ValueError(f'solve_mask: {fname} is {img.shape}, the map ({int(nypix)}, {int(nxpix)})')
+    if np.isnan(img).any():
+        raise ValueError(f'solve_mask: {fname} holds a NaN')
+    return img != 0
+
+
+def _mask_spec(v):
+    """``main``'s solve_mask as None, a file name or ('snr', nsigma, grow); ValueError otherwise."""
+    if v is None or v is False:
+        return None
+    if isinstance(v, str):
+        if v == 'snr':
+            raise ValueError('solve_mask snr needs <nsigma>: snr, <nsigma>[, <grow>]')
+        return v
+    if isinstance(v, (tuple, list)) and len(v) in (2, 3) and v[0] == 'snr':
+        try:
+            nsigma, grow = _snr_spec(tuple(v))
+        except (TypeError, ValueError):
+            raise ValueError(f'solve_mask must be a FITS file or snr, <nsigma>[, <grow>], not {v!r}') from None
+        return ('snr', nsigma, grow)
+    raise ValueError(f'solve_mask must be a FITS file or snr, <nsigma>[, <grow>], not {v!r}')
+
+
+def mask_params(params):
+    """``main``'s solve_mask from the [Inputs] section: ``solve_mask : <file.fits>`` or ``solve_mask :
+    snr, <nsigma>[, <grow>]``; an absent key, None or False means off.  ValueError for anything else."""
+    return _mask_spec(params.get('solve_mask'))
 
 
 def _prior_spec(v):
@@ -354,4 +415,4 @@ def cli(argv):
                 niter=int(params['niter']), healpix=params['healpix'],
                 ground=bool(params.get('ground_template', False)),
                 split=[str(k) for k in as_list(split)] if split else None, residuals=residuals,
-                residual_cut=residual_cut, noise_prior=prior_params(params))
+                residual_cut=residual_cut, noise_prior=prior_params(params), solve_mask=mask_params(params))

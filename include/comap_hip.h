@@ -490,6 +490,29 @@ int comap_destripe_prior_apply_dot(comap_prior *pr, const double *v_dev, double 
 int comap_destripe_prior_solve(comap_prior *pr, double threshold, int32_t niter, double *x_dev, double *map_dev,
                                double *naive_dev, double *weight_dev, double *hits_dev, int32_t *iters_out);
 
+/* ------------------------------------------------------------ destriper solve mask */
+/* A solve mask (MADAM's "inmask") fits the offsets from the samples outside a set of map pixels:
+ * mask_dev holds one uint8 flag per pixel of the problem's pixel order, w'_i = 0 where pixels[i] >= 0
+ * and mask[pixels[i]] != 0, else w_i.  Off-map samples (negative ids) keep their weight; their wrapped
+ * read m[npix + p] sees 0 on a masked pixel, as the reference's operator on w' does.  The CG solves the
+ * reference system built from w'; every output after it (map, naive, weight, hits, split maps,
+ * residuals) uses the full w.  An offset with no unmasked weight has a zero row and b' = 0: the CG
+ * never moves it from +0.0.
+ * comap_destripe_mask_view returns that system as a second comap_destriper, a view of d: it borrows d's
+ * index structure (d must outlive it: comap_destripe_destroy(d) returns -1 while a view lives) and owns
+ * the masked coefficients, sum w' / sum w' tod per offset (d's values bit for bit on every offset that
+ * lost no entry, the others re-summed from the samples in a fixed order), the weight map and naive
+ * numerator with +0.0 on the masked pixels, and its own CG state.  pixels_dev / tod_dev / weights_dev
+ * are the arrays d was created from.  Every comap_destripe_* call and comap_destripe_prior_create take
+ * the view as they take d; comap_destripe_destroy(view) frees what it owns.  -1 for a view of a view. */
+int comap_destripe_mask_view(comap_destriper *d, const int32_t *pixels_dev, const double *tod_dev,
+                             const double *weights_dev, const uint8_t *mask_dev, comap_destriper **view_out);
+/* comap_destripe_solve's CG on a view (graph replay by the same rule), then the final maps binned from
+ * the view's parent with the CG's own x, on the same stream with no host wait between.
+ * comap_destripe_prior_solve on a prior created on a view ends the same way. */
+int comap_destripe_solve_view(comap_destriper *view, double threshold, int32_t niter, double *x_dev, double *map_dev,
+                              double *naive_dev, double *weight_dev, double *hits_dev, int32_t *iters_out);
+
 /* ------------------------------------------------------------ split maps (Destriper.py:487-501) */
 /* Per-label maps of a solved problem, all labels in one pass: the reference's (commented)
  * "Create individual feed maps too" block for any labelling of the offsets.  label_dev[o] in
