@@ -7,7 +7,10 @@ the projections the COMAP configs use -- CAR (cylindrical, (phi0, theta0) =
 (0, 0)), SIN and TAN (zenithal, (0, 90)) -- with CDELT scaling and default
 LONPOLE/LATPOLE, following wcslib's celset/sphs2x conventions.  Pinned against
 astropy 4.3.1 / wcslib by tests/test_astro_golden.py (<= 1.2e-9 px, identical
-pixel ids); the device path receives the pixel ids computed here.
+pixel ids).  The device computes its own pixel ids (wcs_pixel in
+csrc/prep_kernels.hip, the same formulae); this module is their pinned host
+statement, and tests/test_gpu_prep_gather.py holds the device to the same
+astropy vectors.
 
 Also: J2000 equatorial -> galactic (the healpy Rotator(coord=['C','G']) the
 reference applies for GLON-/GLAT- maps, COMAPData.py:411-415).

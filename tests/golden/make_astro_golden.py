@@ -100,9 +100,42 @@ def main():
     out['gal_dec'] = dec
     out['gal_l'] = np.asarray(g.l.deg)
     out['gal_b'] = np.asarray(g.b.deg)
+    # the zenithal maps' central row: sphs2x replaces the native-longitude x by a
+    # cancellation-free form where |x| < 1e-5, a band a few hundredths of a pixel wide
+    # along the row through CRPIX2 that the random points above never enter (these
+    # come from pixel coordinates, not from rng: the draws above keep their values)
+    for name, crval, cdelt, crpix, ctype, nx, ny in MAPS:
+        if name not in ('sin', 'tan'):
+            continue
+        w = WCS(naxis=2)
+        w.wcs.crval = crval
+        w.wcs.cdelt = cdelt
+        w.wcs.crpix = crpix
+        w.wcs.ctype = ctype
+        rows = (crpix[1] - 1) + np.array([0.0, 0.003, -0.003, 0.02, -0.02, 0.2])
+        gx, gy = np.meshgrid(np.arange(3, nx, 29) + 0.31, rows)
+        lon, lat = w.wcs_pix2world(gx.ravel(), gy.ravel(), 0)
+        px, py = w.wcs_world2pix(lon, lat, 0)
+        out[f'wcs_{name}_row_lon'] = lon
+        out[f'wcs_{name}_row_lat'] = lat
+        out[f'wcs_{name}_row_px'] = px
+        out[f'wcs_{name}_row_py'] = py
     import astropy
     out['astropy_version'] = np.array(astropy.__version__)
-    np.savez_compressed(os.path.join(HERE, 'golden_astro.npz'), **out)
+    path = os.path.join(HERE, 'golden_astro.npz')
+    if os.path.exists(path):
+        # a regeneration changes no vector already committed: wcslib's and erfa's results
+        # reproduce bit for bit; gal_l / gal_b go through a matrix product whose last bit
+        # depends on the BLAS build (5.7e-14 deg seen), so they are checked to 1e-12 deg
+        # and the committed values are kept
+        old = np.load(path)
+        for k in old.files:
+            if k in ('gal_l', 'gal_b'):
+                assert np.max(np.abs(old[k] - out[k])) < 1e-12, f'{k} would change'
+                out[k] = old[k]
+            else:
+                assert np.array_equal(old[k], out[k]), f'{k} would change'
+    np.savez_compressed(path, **out)
     print('wrote golden_astro.npz with astropy', astropy.__version__)
 
 

@@ -6,7 +6,9 @@ astropy; the pipeline's Python does not).
 * WCS world -> pixel (wcslib): our Calabretta & Greisen restatement
   (mapmaking/wcs.py) agrees to ~1e-12 px for CAR and ~1e-9 px for SIN / TAN, and
   COMAPData.transform_to_1d's pixel ids are identical on every point, including a
-  grid placed 0.01 px from the floor(p + 0.5) edges.
+  grid placed 0.01 px from the floor(p + 0.5) edges, and points on the zenithal
+  maps' row through CRPIX2, where the native longitude takes its small-x form.
+  (tests/test_gpu_prep_gather.py holds the device's own copy to the same vectors.)
 * J2000 -> galactic: mapmaking/wcs.equatorial_to_galactic to 1e-5 deg of astropy's
   FK5 -> Galactic.  The reference itself rotates with healpy's
   Rotator(coord=['C','G']) (its ecliptic-based matrix, restated in astro.Rotator),
@@ -61,6 +63,35 @@ def test_wcs_world2pix_vs_wcslib(golden, name, crval, cdelt, crpix, ctype, nx, n
     idx = transform_to_1d(lon, lat, w, nx, ny)
     assert np.array_equal(idx, ref.astype(int))
     assert (idx >= 0).sum() > 1000 and (idx < 0).sum() > 100      # on- and off-map points
+
+
+def native_x(w, lon, lat):
+    """The native-longitude x of CelestialWCS._native before its small-x replacement
+    (wcslib sphs2x switches to a cancellation-free form where |x| < 1e-5)."""
+    D2R = np.pi / 180.0
+    e0, _, _, ce1, se1 = w.eul
+    return np.sin(lat * D2R) * se1 - np.cos(lat * D2R) * ce1 * np.cos((lon - e0) * D2R)
+
+
+@pytest.mark.parametrize('name,crval,cdelt,crpix,ctype,nx,ny,tol', MAPS[3:], ids=[m[0] for m in MAPS[3:]])
+def test_wcs_central_row_small_x_vs_wcslib(golden, name, crval, cdelt, crpix, ctype, nx, ny, tol):
+    """The zenithal maps' row through CRPIX2, where sphs2x replaces x (|x| < 1e-5): points
+    0, +-0.003, +-0.02 and 0.2 px from it, the same checks as on the scattered points."""
+    w = CelestialWCS(crval, cdelt, crpix, ctype)
+    lon, lat = golden[f'wcs_{name}_row_lon'], golden[f'wcs_{name}_row_lat']
+    rx, ry = golden[f'wcs_{name}_row_px'], golden[f'wcs_{name}_row_py']
+    assert 2 * np.sum(np.abs(native_x(w, lon, lat)) < 1e-5) >= lon.size
+    px, py = w.wcs_world2pix(lon, lat, 0)
+    assert np.all(np.isfinite(rx)) and np.all(np.isfinite(px))
+    assert np.max(np.abs(px - rx)) < tol and np.max(np.abs(py - ry)) < tol
+    qx, qy = np.floor(rx + 0.5), np.floor(ry + 0.5)
+    qx[(qx < 0) | (qx > nx - 1)] = np.nan
+    qy[(qy < 0) | (qy > ny - 1)] = np.nan
+    ref = qy * nx + qx
+    ref[np.isnan(ref)] = -1
+    assert np.array_equal(transform_to_1d(lon, lat, w, nx, ny), ref.astype(int))
+    # none of the scattered points is in the band: this fixture is its only cover
+    assert not np.any(np.abs(native_x(w, golden[f'wcs_{name}_lon'], golden[f'wcs_{name}_lat'])) < 1e-5)
 
 
 def test_equatorial_to_galactic_vs_astropy(golden):
